@@ -18,14 +18,19 @@ non-zero status; every rank checks that its process group has exactly N members.
 
 N=1 workload: BASELINE config C3 (32,768 envs, 256x256 grid, 16 moving discs,
 180-beam lidar) — the largest single-GPU config and the one the north-star
-target (256x256, 32k envs) is quoted on.  Every run has two legs:
+target (256x256, 32k envs) is quoted on.  A plain run does what the line's `value` needs and
+nothing else: it builds the instance, warms up, times the K steps (`ms_per_step`), writes the last
+timed step's outputs if --dump-outputs DIR is given, and prints the line.  --full adds the rest: a
+run then has two legs
 
   weak    C3 per rank (32,768 envs on each of the N GPUs) — the line's `value`
   strong  C4: 65,536 envs split over the N ranks (`strong`; --strong-config none skips)
 
-so the driver's 1/2/4/8-GPU runs yield both scaling curves.  No data-path collective
-(env shards; one max-reduce of the timings).  --config C4/C5 makes the main leg
-split its total over the ranks instead.  Rank 0 prints ONE JSON line.
+so 1/2/4/8-GPU runs with --full yield both scaling curves, plus the closed-loop forms of the main
+leg (`closed_loop`), the compact-layout leg (`compact_layout`) and the CPU baseline
+(`cpu_baseline`).  No data-path collective (env shards; one max-reduce of the timings).
+--config C4/C5 makes the main leg split its total over the ranks instead.  Rank 0 prints ONE
+JSON line.
 """
 from __future__ import annotations
 
@@ -42,7 +47,7 @@ METRIC = "env-steps/sec (batched gym_ffmp) at 1/2/4/8 MI355X; HBM-roofline %"
 PEAK_HBM_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s)
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
@@ -94,7 +99,73 @@ def parse():
                         "(obs_format=u8f16), reported as `compact_layout` beside the metric (0 = skip)")
     p.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                    help="nccl (= RCCL on ROCm) for real runs; gloo only to rehearse several ranks on one GPU")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: the closed-loop forms (--closed-loop), the "
+                        "compact-layout leg (--compact-steps), the strong-scaling leg (--strong-config) and the CPU "
+                        "baseline (--cpu-seconds); without it those options are ignored and their keys are null or absent")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned (obs, reward, done, info) as "
+                        "DIR/<name>.npy in float32 (the big planes: a fixed seeded sample of envs, sample_envs.npy; "
+                        "+-inf lidar ranges as +-the largest float32); "
+                        "ranks beyond the first write to DIR/rank<r>/")
+    args = p.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.closed_loop, args.compact_steps, args.strong_config, args.cpu_seconds = 0, 0, "none", 0.0
+    return args
+
+
+DUMP_PLANE_BYTES = 24 << 20  # --dump-outputs: the sampled planes (state_m, potential, flow) together
+DUMP_ROW_BYTES = 32 << 20    # ... and the per-env vectors together (all envs if they fit)
+
+
+def dump_outputs(env, path: str) -> dict:
+    """Write the observation, reward, done and info of the step the env just ran (what step() returns,
+    or a graph replay leaves in the same buffers) as float32 .npy files under `path`.  The planes
+    ((N, 2, G, G) state_m, (N, G, G) potential, flow) are written for a fixed seeded sample of envs
+    (sample_envs.npy: their indices), the per-env vectors for every env while they fit
+    DUMP_ROW_BYTES (else for a second fixed sample, row_envs.npy).  Every written value is finite:
+    the lidar's "no return" (+inf) and "origin inside a disc" (-inf) are written as +-the largest
+    float32, far outside any range, so the files compare with plain arithmetic (a NaN, which no
+    output holds by specification, would be written as 0 and counted).  Returns ({name: shape},
+    {name: {"posinf" / "neginf" / "nan": count}} of the arrays that held such values)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = env.num_envs
+    obs = env.obs
+    planes = {k: obs[k] for k in ("state_m", "potential", "flow") if k in obs}
+    rows = {k: v for k, v in obs.items() if k not in planes}
+    rows.update(reward=env.reward, done=env.done, is_goal=env.is_goal, collision=env.collision,
+                truncated=env.truncated, step=env.t, episode=env.episode)
+    per_env = 4 * sum(v[0].numel() for v in planes.values())  # as float32
+    idx = np.sort(np.random.default_rng(20240).choice(n, size=min(n, max(1, DUMP_PLANE_BYTES // per_env)),
+                                                      replace=False))
+    row_bytes = 4 * sum(v[0].numel() for v in rows.values())
+    ridx = None
+    if n * row_bytes > DUMP_ROW_BYTES:
+        ridx = np.sort(np.random.default_rng(20241).choice(n, size=DUMP_ROW_BYTES // row_bytes, replace=False))
+    written, nonfinite = {}, {}
+    big = float(np.finfo(np.float32).max)
+
+    def save(name, a):
+        a = np.array(a, dtype=np.float32, order="C")
+        if not np.isfinite(a).all():
+            nonfinite[name] = {"posinf": int(np.isposinf(a).sum()), "neginf": int(np.isneginf(a).sum()),
+                               "nan": int(np.isnan(a).sum())}
+            np.nan_to_num(a, copy=False, nan=0.0, posinf=big, neginf=-big)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+
+    it = torch.as_tensor(idx, device=env.device)
+    for k, v in planes.items():
+        save(k, v[it].float().cpu().numpy())
+    save("sample_envs", idx)
+    rt = None if ridx is None else torch.as_tensor(ridx, device=env.device)
+    for k, v in rows.items():
+        save(k, (v if rt is None else v[rt]).float().cpu().numpy())
+    if ridx is not None:
+        save("row_envs", ridx)
+    return written, nonfinite
 
 
 def _time_oracle(env, n, seconds: float, seed: int):
@@ -458,12 +529,13 @@ def run_leg(args, name, cfg, n, offset, K, W, dev, world, rank, strong, main_leg
         # (profiles/r03b_transient*.txt) — at the 8-GPU strong leg's 0.6-ms steps the driver's 20 timed
         # steps fell to 0.80 of the roofline from 0.90 at 200 (profiles/r06a_bench_c4_8192_*.json).  Replay
         # the graph for >= 30 ms of GPU work (untimed, the warm-up's actions) right before the timed region.
-        t_one = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t_one[0].record()
-        graph.replay(actions[:per])
-        t_one[1].record()
-        torch.cuda.synchronize()
-        for _ in range(max(1, int(30.0 / max(t_one[0].elapsed_time(t_one[1]), 1e-3)))):
+        # The replay count comes from the replay's bytes at the HBM peak (a replay never runs faster), not
+        # from a measured time: these replays step the envs, and the same arguments must bring every run
+        # to the same state at the first timed step (--dump-outputs).  One replay, then 30 ms worth, as
+        # when the first one was timed (C3: 17 ms at the peak, 1 + 1 replays); at most 64 in all.
+        peak_ms = graph_bytes / (PEAK_HBM_GBS * 1e6)
+        rewarm = 1 + min(63, max(1, int(30.0 / max(peak_ms, 1e-3))))
+        for _ in range(rewarm):
             graph.replay(actions[:per])
         torch.cuda.synchronize()
     ep0_t = env.episode.sum()  # read after the loop: no host round trip between the sync and the loop
@@ -495,6 +567,10 @@ def run_leg(args, name, cfg, n, offset, K, W, dev, world, rank, strong, main_leg
     el_local = time.perf_counter() - t0
     env.check_errors()
     resets = int(env.episode.sum()) - int(ep0_t)  # auto-resets in the timed steps
+    dumped = None
+    if args.dump_outputs and main_leg:  # the last timed step's outputs, before anything steps the env again
+        dumped = dump_outputs(env, args.dump_outputs if rank == 0 else
+                              os.path.join(args.dump_outputs, f"rank{rank}"))
 
     # the dominant kernel — the raster, or with the one-launch step the fused env-step + raster
     # kernel: HIP events around every launch on the launch stream; algorithmic bytes per launch
@@ -538,7 +614,9 @@ def run_leg(args, name, cfg, n, offset, K, W, dev, world, rank, strong, main_leg
         "pool_released_bytes": getattr(env, "pool_released_bytes", 0),
         "frame_window": env.frame_window, "ring": env.ring, "fused": bool(env.fused),
         "graph": ({"steps_per_replay": per, "replays": K // per, "remainder_steps": rem,
-                   "skewed": bool(graph.skewed), "skew_trial": skew_trial} if graph is not None else
+                   "skewed": bool(graph.skewed), "skew_trial": skew_trial,
+                   # whole replays of the warm-up's first actions between the warm-up and the timed steps
+                   "rewarm_replays": rewarm} if graph is not None else
                   {"error": graph_error} if graph_error else None),
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                      "frac": achieved / PEAK_HBM_GBS,
@@ -560,6 +638,7 @@ def run_leg(args, name, cfg, n, offset, K, W, dev, world, rank, strong, main_leg
         "hbm_roofline_pct_whole_step": 100.0 * (b["total"] * n_total * K / el / 1e9) / (PEAK_HBM_GBS * world),
         "per_launch_envs": raster_ev[0][2],
         "closed_loop": closed,
+        "dumped_outputs": dumped,
     }
     if closed is not None:
         for k in ("step_graph", "step_plain", "policy_graph"):
@@ -823,6 +902,9 @@ def main():
         }
         if leg.get("closed_loop") is not None:
             out["closed_loop"] = leg["closed_loop"]
+        if leg.get("dumped_outputs") is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": leg["dumped_outputs"][0],
+                                     "nonfinite_written_finite": leg["dumped_outputs"][1]}
         if strong_leg is not None:
             out["strong"] = strong_leg
         if compact is not None:
