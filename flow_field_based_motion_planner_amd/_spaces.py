@@ -18,6 +18,27 @@ except Exception:  # noqa: BLE001
             self.high = np.asarray(high)
             self.dtype = np.dtype(dtype)
             self.shape = self.low.shape if shape is None else tuple(shape)
+            self._rng = np.random.default_rng()
+
+        def seed(self, seed=None):
+            self._rng = np.random.default_rng(seed)
+            return [seed]
+
+        def sample(self):
+            """As gym.spaces.Box.sample: uniform between finite bounds; normal where unbounded,
+            shifted exponential where bounded on one side."""
+            lo = np.broadcast_to(self.low, self.shape).astype(np.float64)
+            hi = np.broadcast_to(self.high, self.shape).astype(np.float64)
+            if self.dtype.kind != "f":
+                hi = hi + 1.0  # integers: floor of uniform [low, high + 1)
+            flo, fhi = np.isfinite(lo), np.isfinite(hi)
+            x = self._rng.normal(size=self.shape)
+            x = np.where(flo & fhi, self._rng.uniform(np.where(flo, lo, 0.0), np.where(fhi & flo, hi, 1.0)), x)
+            x = np.where(flo & ~fhi, np.where(flo, lo, 0.0) + self._rng.exponential(size=self.shape), x)
+            x = np.where(~flo & fhi, np.where(fhi, hi, 0.0) - self._rng.exponential(size=self.shape), x)
+            if self.dtype.kind != "f":
+                x = np.floor(x)
+            return np.clip(x, self.low, self.high).astype(self.dtype)
 
         def contains(self, x):
             x = np.asarray(x)

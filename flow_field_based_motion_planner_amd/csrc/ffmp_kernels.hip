@@ -250,15 +250,23 @@ FFMP_DEV void stage_footprint(const ffmp_cfg_t& cfg, float2* s_foot) {
   if ((threadIdx.x & 63) == 0) s_foot[FFMP_MAX_FOOT] = make_float2(bx, by);
 }
 
+// The element type of a step's `action` array: an action id, or a (v, w) command (env_group's CMD).
+template <bool CMD>
+using act_t = std::conditional_t<CMD, double2, int64_t>;
+
 // LPE lanes per env (16, 32 or 64 >= K): a wave serves 64 / LPE envs, so the per-env scalar
 // float64 work (integrator, trig, goal, reward, record header) is issued once per 64/LPE envs
 // instead of once per env; lane k of an env's group holds its obstacle k, beams and footprint
 // cells are strided over the group's lanes.
 // One env's step (or reset) by its LPE-lane group: lane = the lane within the group, s_* = the
 // group's LDS slices (FFMP_MAX_OBST entries each).  Used by env_kernel and step_raster_kernel.
-template <int MODE, int LPE, int BCH = FFMP_BEAM_CHUNK, bool DL = false, int DPL = 1>
+// CMD (SPEC a15b): the step's command source, fixed at compile time — false: action[e] is an action
+// id (int64, the 28-entry table); true: action[e] is the env's continuous (v, w) command (two
+// float64, one 16-byte load), clipped to the table's bounds.  Everything after the command is the
+// same code, so a command equal to a table entry steps bit-identically to that entry's id.
+template <int MODE, int LPE, int BCH = FFMP_BEAM_CHUNK, bool DL = false, int DPL = 1, bool CMD = false>
 FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, int64_t env_offset,
-                                                       const int64_t* __restrict__ action, int32_t initial,
+                                                       const act_t<CMD>* __restrict__ action, int32_t initial,
                                                        const ffmp_state_t& st, const ffmp_obs_t& ob,
                                                        const ffmp_out_t& out, int64_t e, int lane, double* s_ox,
                                                        double* s_oy, double* s_or, double* s_orr, float4* s_ecur,
@@ -303,12 +311,30 @@ FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, in
 
   if (MODE == kEnvMode_Step) {
     // ---- action -> (v, w) (train.py:668-673 -> Gazebo /cmd_vel) ----
-    int64_t a = action[e];
-    if (a < 0 || a >= FFMP_N_ACTIONS) {
-      if (lane == 0) atomicOr(st.err, 1u);
-      a = 3;  // (0.0, 0.0)
+    double v, w;
+    if constexpr (CMD) {
+      // a continuous command (the Box of ffmp.py:29-32; train.py:134-143 publishes any Twist): NaN
+      // runs (0, 0) and sets error bit 2; the rest is clipped to the table's bounds cmd[0], cmd[27]
+      // (+-inf clips, -0.0 passes through)
+      const double2 c = action[e];
+      v = c.x;
+      w = c.y;
+      if (v != v || w != w) {
+        if (lane == 0) atomicOr(st.err, 2u);
+        v = 0.0;
+        w = 0.0;
+      }
+      v = v < 0.0 ? 0.0 : (v > 0.6 ? 0.6 : v);
+      w = w < -0.6 ? -0.6 : (w > 0.6 ? 0.6 : w);
+    } else {
+      int64_t a = action[e];
+      if (a < 0 || a >= FFMP_N_ACTIONS) {
+        if (lane == 0) atomicOr(st.err, 1u);
+        a = 3;  // (0.0, 0.0)
+      }
+      v = cmd_v((int)a / 7);
+      w = cmd_w((int)a % 7);
     }
-    const double v = cmd_v((int)a / 7), w = cmd_w((int)a % 7);
     // ---- unicycle integrator (SPEC a15) ----
     c0 = cos(yaw0);
     s0 = sin(yaw0);
@@ -552,9 +578,9 @@ FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, in
 #else
 #define FFMP_ENV_OCC
 #endif
-template <int MODE, int kEnvWaves, int LPE, int DPL>
+template <int MODE, int kEnvWaves, int LPE, int DPL, bool CMD = false>
 __global__ __launch_bounds__(64 * kEnvWaves) FFMP_ENV_OCC void env_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
-                                                 const int64_t* __restrict__ action,
+                                                 const act_t<CMD>* __restrict__ action,
                                                  const uint8_t* __restrict__ mask, int32_t initial,
                                                  ffmp_state_t st, ffmp_obs_t ob, ffmp_out_t out) {
   constexpr int EPW = 64 / LPE;  // envs per wave
@@ -575,7 +601,7 @@ __global__ __launch_bounds__(64 * kEnvWaves) FFMP_ENV_OCC void env_kernel(ffmp_c
   if (e >= n) return;
   if (MODE == kEnvMode_Reset && mask && !mask[e]) return;
   const int g0 = grp * LPE * DPL;  // the env's disc slots
-  env_group<MODE, LPE, FFMP_BEAM_CHUNK, true, DPL>(cfg, env_offset, action, initial, st, ob, out, e, lane,
+  env_group<MODE, LPE, FFMP_BEAM_CHUNK, true, DPL, CMD>(cfg, env_offset, action, initial, st, ob, out, e, lane,
                        s_oxa[wv] + g0, s_oya[wv] + g0, s_ora[wv] + g0, s_orra[wv] + g0,
                        s_ecura[wv] + g0, s_epreva[wv] + g0, s_foota[wv], nullptr, nullptr,
                        s_keys + ((size_t)wv * EPW + grp) * cfg.n_beams, s_prefa[wv] + g0, s_loa[wv] + g0);
@@ -1144,9 +1170,9 @@ __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES 
 template <bool FLOW, int FMT>
 constexpr int kFusedMinWaves = (FMT == FMT_CT4 && !FLOW) ? 7 : (FMT == FMT_CT8 && !FLOW) ? FFMP_CT8_MIN_WAVES : 1;
 
-template <bool NT, bool XCD, bool FLOW, int FMT>
+template <bool NT, bool XCD, bool FLOW, int FMT, bool CMD = false>
 __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
-                                                          const int64_t* __restrict__ action, ffmp_state_t st,
+                                                          const act_t<CMD>* __restrict__ action, ffmp_state_t st,
                                                           ffmp_obs_t ob, ffmp_out_t out, int64_t sm_stride,
                                                           int64_t sm_frame, int32_t newest_only,
                                                           int32_t tile_log2r) {
@@ -1162,7 +1188,7 @@ __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_
     stage_footprint(cfg, s_foot);
     // (one beam at a time where the block is held to more than 4 waves per SIMD: the chunked
     // lidar's registers would spill there)
-    env_group<kEnvMode_Step, 64, (kFusedMinWaves<FLOW, FMT> > 4 ? 1 : FFMP_BEAM_CHUNK)>(cfg, env_offset, action, 0, st, ob, out, e, (int)threadIdx.x, s_ox, s_oy, s_or,
+    env_group<kEnvMode_Step, 64, (kFusedMinWaves<FLOW, FMT> > 4 ? 1 : FFMP_BEAM_CHUNK), false, 1, CMD>(cfg, env_offset, action, 0, st, ob, out, e, (int)threadIdx.x, s_ox, s_oy, s_or,
                                  s_orr, s_ecur, s_eprev, s_foot, s_hdr, FLOW ? s_vel : nullptr);
   }
   // The record reaches the raster through LDS: env_group left its ego discs of both frames in
@@ -1488,13 +1514,13 @@ size_t device_lds_limit() {
 // false (nothing launched) when the block's LDS — the static disc / footprint arrays, which grow
 // with the discs per lane, plus trace_discs' dynamic beam minima (W x envs per wave x L words) —
 // exceeds what a block may use: the caller then tries a layout that needs less
-template <int MODE, int W, int LPE, int DPL>
-bool launch_env_t(const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset, const int64_t* action, const uint8_t* mask,
+template <int MODE, int W, int LPE, int DPL, bool CMD>
+bool launch_env_t(const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset, const void* action, const uint8_t* mask,
                   int32_t initial, const ffmp_state_t& st, const ffmp_obs_t& ob, const ffmp_out_t& o,
                   hipStream_t s) {
   static const size_t static_lds = [] {
     hipFuncAttributes a{};
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&env_kernel<MODE, W, LPE, DPL>)) == hipSuccess
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&env_kernel<MODE, W, LPE, DPL, CMD>)) == hipSuccess
                ? (size_t)a.sharedSizeBytes
                : (size_t)0;
   }();
@@ -1502,19 +1528,19 @@ bool launch_env_t(const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset, const in
   const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
   const size_t lds = (size_t)W * (64 / LPE) * (size_t)cfg.n_beams * sizeof(uint32_t);  // trace_discs' beam minima
   if (static_lds + lds > device_lds_limit()) return false;
-  hipLaunchKernelGGL((env_kernel<MODE, W, LPE, DPL>), dim3(blocks), dim3(64 * W), lds, s, cfg, n, env_offset, action,
-                     mask, initial, st, ob, o);
+  hipLaunchKernelGGL((env_kernel<MODE, W, LPE, DPL, CMD>), dim3(blocks), dim3(64 * W), lds, s, cfg, n, env_offset,
+                     static_cast<const act_t<CMD>*>(action), mask, initial, st, ob, o);
   return true;
 }
 
 // (lanes per env, discs per lane) pairs with an env_kernel instance; false if there is none or its
 // block would not fit the LDS
-template <int MODE, int W>
-bool launch_env_mode(int lpe, int dpl, const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset, const int64_t* action,
+template <int MODE, int W, bool CMD>
+bool launch_env_mode(int lpe, int dpl, const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset, const void* action,
                      const uint8_t* mask, int32_t initial, const ffmp_state_t& st, const ffmp_obs_t& ob,
                      const ffmp_out_t& o, hipStream_t s) {
 #define FFMP_ENV_CASE(L_, D_)                                                                    \
-  if (lpe == L_ && dpl == D_) return launch_env_t<MODE, W, L_, D_>(cfg, n, env_offset, action, mask, initial, st, ob, o, s);
+  if (lpe == L_ && dpl == D_) return launch_env_t<MODE, W, L_, D_, CMD>(cfg, n, env_offset, action, mask, initial, st, ob, o, s);
   FFMP_ENV_CASE(16, 1) FFMP_ENV_CASE(32, 1) FFMP_ENV_CASE(64, 1) FFMP_ENV_CASE(8, 2) FFMP_ENV_CASE(16, 2)
   FFMP_ENV_CASE(4, 4) FFMP_ENV_CASE(8, 1)
 #undef FFMP_ENV_CASE
@@ -1522,12 +1548,14 @@ bool launch_env_mode(int lpe, int dpl, const ffmp_cfg_t& cfg, int64_t n, int64_t
 }
 
 template <int W>
-bool launch_env_lpe(int mode, int lpe, int dpl, const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset,
-                    const int64_t* action, const uint8_t* mask, int32_t initial, const ffmp_state_t& st,
+bool launch_env_lpe(int mode, bool cmd, int lpe, int dpl, const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset,
+                    const void* action, const uint8_t* mask, int32_t initial, const ffmp_state_t& st,
                     const ffmp_obs_t& ob, const ffmp_out_t& o, hipStream_t s) {
+  if (mode == kEnvMode_Step && cmd)  // `action` holds (v, w) commands (ffmp_step_state_cmd)
+    return launch_env_mode<kEnvMode_Step, W, true>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
   if (mode == kEnvMode_Step)
-    return launch_env_mode<kEnvMode_Step, W>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
-  return launch_env_mode<kEnvMode_Reset, W>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
+    return launch_env_mode<kEnvMode_Step, W, false>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
+  return launch_env_mode<kEnvMode_Reset, W, false>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
 }
 
 // ============================================================================
@@ -1664,6 +1692,28 @@ __global__ __launch_bounds__(256) void policy_reactive_kernel(int64_t n, int32_t
     if (wi == 3) wi = 6;  // obstacle straight ahead and the goal too: turn on the spot (left)
   }
   action[e] = 7 * vi + wi;
+}
+
+// The field follower of ffmp_policy_field: one lane per env turns the potential's gradient at the
+// robot cell (obs.grad, ego frame, x = heading) into a (v, w) command that descends it.  Every
+// operation is a float64 + - x / sqrt or a compare, in this order (no contraction in this file), so
+// a NumPy restatement gives the same bits (tests/test_gpu_commands.py).
+__global__ __launch_bounds__(256) void policy_field_kernel(int64_t n, double dt, const float* __restrict__ grad,
+                                                           double2* __restrict__ cmd) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n) return;
+  const double gx = (double)grad[e * 2 + 0], gy = (double)grad[e * 2 + 1];
+  const double m2 = gx * gx + gy * gy;
+  double v = 0.0, w = 0.0;
+  if (m2 > 0.0 && m2 - m2 == 0.0) {  // a finite, non-zero gradient
+    const double m = sqrt(m2);
+    const double dx = -gx / m, dy = -gy / m;  // unit descent direction
+    w = dy / dt;                              // turn the heading onto it within one step ...
+    w = w < -0.6 ? -0.6 : (w > 0.6 ? 0.6 : w);
+    if (dx < 0.0) w = dy >= 0.0 ? 0.6 : -0.6;  // ... unless it points behind the robot: turn on the spot
+    v = 0.6 * (dx > 0.0 ? dx : 0.0);
+  }
+  cmd[e] = make_double2(v, w);
 }
 
 // Calls f(NT, XCD, FLOW, FMT) with std::integral_constant arguments for the runtime choice (the
@@ -1808,8 +1858,8 @@ int ffmp_footprint(int32_t grid, double res, double robot_r, int32_t* di, int32_
   return cnt;
 }
 
-static int launch_env(int mode, const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset,
-                      const int64_t* action, const uint8_t* mask, int32_t initial,
+static int launch_env(int mode, bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset,
+                      const void* action, const uint8_t* mask, int32_t initial,
                       ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, void* stream) {
   int rc = check_cfg(cfg);
   if (rc) return rc;
@@ -1822,7 +1872,8 @@ static int launch_env(int mode, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
     return fail(FFMP_E_ARG, "an obs pointer is NULL");
   if (cfg->n_beams > 0 && !obs->lidar) return fail(FFMP_E_ARG, "obs.lidar NULL with n_beams > 0");
   if (mode == kEnvMode_Step) {
-    if (!action) return fail(FFMP_E_ARG, "action is NULL");
+    if (!action) return fail(FFMP_E_ARG, cmd ? "cmd is NULL" : "action is NULL");
+    if (cmd && ((uintptr_t)action & 15u) != 0) return fail(FFMP_E_ARG, "cmd must be 16-byte aligned");
     if (!out || !out->reward || !out->done || !out->is_goal || !out->collide || !out->truncated)
       return fail(FFMP_E_ARG, "an out pointer is NULL");
   }
@@ -1848,8 +1899,8 @@ static int launch_env(int mode, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   const hipStream_t hs = (hipStream_t)stream;
   const bool w4 = tu.env_waves == 4;
   auto try_launch = [&](bool four, int l, int d) {
-    return four ? launch_env_lpe<4>(mode, l, d, *cfg, n, env_offset, action, mask, initial, *state, *obs, o, hs)
-                : launch_env_lpe<1>(mode, l, d, *cfg, n, env_offset, action, mask, initial, *state, *obs, o, hs);
+    return four ? launch_env_lpe<4>(mode, cmd, l, d, *cfg, n, env_offset, action, mask, initial, *state, *obs, o, hs)
+                : launch_env_lpe<1>(mode, cmd, l, d, *cfg, n, env_offset, action, mask, initial, *state, *obs, o, hs);
   };
   // the tuned layout; one wave per block (a quarter of the LDS); one disc per lane on the fewest
   // lanes that hold the discs (the smallest static arrays) — the last always fits (64 lanes x 1
@@ -1859,17 +1910,22 @@ static int launch_env(int mode, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   if (!ok)
     return fail(FFMP_E_ARG, "no env_kernel layout fits the %zu B of LDS a block may use (K = %d, L = %d)",
                 device_lds_limit(), cfg->n_obst, cfg->n_beams);
-  return check_launch(mode == kEnvMode_Step ? "ffmp_step_state" : "ffmp_reset");
+  return check_launch(mode != kEnvMode_Step ? "ffmp_reset" : cmd ? "ffmp_step_state_cmd" : "ffmp_step_state");
 }
 
 int ffmp_reset(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const uint8_t* mask,
                int32_t initial, ffmp_state_t* state, ffmp_obs_t* obs, void* stream) {
-  return launch_env(kEnvMode_Reset, cfg, n, env_offset, nullptr, mask, initial, state, obs, nullptr, stream);
+  return launch_env(kEnvMode_Reset, false, cfg, n, env_offset, nullptr, mask, initial, state, obs, nullptr, stream);
 }
 
 int ffmp_step_state(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action,
                     ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, void* stream) {
-  return launch_env(kEnvMode_Step, cfg, n, env_offset, action, nullptr, 0, state, obs, out, stream);
+  return launch_env(kEnvMode_Step, false, cfg, n, env_offset, action, nullptr, 0, state, obs, out, stream);
+}
+
+int ffmp_step_state_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd,
+                        ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, void* stream) {
+  return launch_env(kEnvMode_Step, true, cfg, n, env_offset, cmd, nullptr, 0, state, obs, out, stream);
 }
 
 int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const uint8_t* mask,
@@ -1948,12 +2004,22 @@ int ffmp_step(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_
   return ffmp_raster(cfg, n, state->record, nullptr, obs, stream);
 }
 
-int ffmp_step_fused(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action,
-                    ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, int32_t flags, void* stream) {
+int ffmp_step_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd, ffmp_state_t* state,
+                  ffmp_obs_t* obs, ffmp_out_t* out, void* stream) {
+  int rc = ffmp_step_state_cmd(cfg, n, env_offset, cmd, state, obs, out, stream);
+  if (rc) return rc;
+  return ffmp_raster(cfg, n, state->record, nullptr, obs, stream);
+}
+
+// ffmp_step_fused (action ids) / ffmp_step_fused_cmd (cmd: `action` holds (n, 2) float64 commands)
+static int step_fused(bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const void* action,
+                      ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, int32_t flags, void* stream) {
   int rc = check_cfg(cfg);
   if (rc) return rc;
   if (n < 0 || env_offset < 0) return fail(FFMP_E_ARG, "negative n or env_offset");
-  if (!state || !obs || !action || !out) return fail(FFMP_E_ARG, "state/obs/action/out is NULL");
+  if (!state || !obs || !action || !out)
+    return fail(FFMP_E_ARG, cmd ? "state/obs/cmd/out is NULL" : "state/obs/action/out is NULL");
+  if (cmd && ((uintptr_t)action & 15u) != 0) return fail(FFMP_E_ARG, "cmd must be 16-byte aligned");
   if (!state->pose || !state->goal || !state->d0 || !state->t || !state->episode || !state->record || !state->err)
     return fail(FFMP_E_ARG, "a state pointer is NULL");
   if (cfg->n_obst > 0 && (!state->obst || !state->obst_r)) return fail(FFMP_E_ARG, "obstacle state NULL");
@@ -1988,10 +2054,24 @@ int ffmp_step_fused(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const 
   hipStream_t s = (hipStream_t)stream;
   ffmp_out_t o = *out;
   dispatch_variant(fmt, nt, xcd, fl, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
-    hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value>), grid, block, tuning().lds_pad, s, *cfg, n,
-                       env_offset, action, *state, *obs, o, sm_stride, sm_frame, newest, tile_log2r);
+    if (cmd)
+      hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value, true>), grid, block, tuning().lds_pad, s, *cfg, n,
+                         env_offset, static_cast<const double2*>(action), *state, *obs, o, sm_stride, sm_frame, newest, tile_log2r);
+    else
+      hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value, false>), grid, block, tuning().lds_pad, s, *cfg, n,
+                         env_offset, static_cast<const int64_t*>(action), *state, *obs, o, sm_stride, sm_frame, newest, tile_log2r);
   });
-  return check_launch("ffmp_step_fused");
+  return check_launch(cmd ? "ffmp_step_fused_cmd" : "ffmp_step_fused");
+}
+
+int ffmp_step_fused(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action,
+                    ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, int32_t flags, void* stream) {
+  return step_fused(false, cfg, n, env_offset, action, state, obs, out, flags, stream);
+}
+
+int ffmp_step_fused_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd,
+                        ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, int32_t flags, void* stream) {
+  return step_fused(true, cfg, n, env_offset, cmd, state, obs, out, flags, stream);
 }
 
 #ifndef FFMP_SKEW_ENV_SPAN
@@ -2327,6 +2407,20 @@ int ffmp_policy_reactive(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs
                        reinterpret_cast<const uint8_t*>(obs->state_m) + frame, env_stride, obs->state_g, look0, look1,
                        1.0f, action);
   return check_launch("ffmp_policy_reactive");
+}
+
+int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, double* cmd, void* stream) {
+  int rc = check_cfg(cfg);
+  if (rc) return rc;
+  if (n < 0) return fail(FFMP_E_ARG, "negative n");
+  if (!obs || !obs->grad) return fail(FFMP_E_ARG, "obs.grad is NULL");
+  if (!cmd) return fail(FFMP_E_ARG, "cmd is NULL");
+  if (((uintptr_t)cmd & 15u) != 0) return fail(FFMP_E_ARG, "cmd must be 16-byte aligned");
+  if (n == 0) return FFMP_OK;
+  if (n > 0x7fffffffLL) return fail(FFMP_E_ARG, "n too large for one launch: %lld", (long long)n);
+  hipLaunchKernelGGL(policy_field_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
+                     cfg->dt, obs->grad, reinterpret_cast<double2*>(cmd));
+  return check_launch("ffmp_policy_field");
 }
 
 #ifdef FFMP_TRACE

@@ -19,8 +19,9 @@ buffer, one copy in, the kernel, one copy out, the stream synchronized; the foot
 (map attributes, width) instead of rebuilt over all G^2 cells per call (ffmp.py:87-94).
 
 New (the reference's reset is commented out, ffmp.py:77-83, and it has no step):
-  reset(seed=None) -> obs,  step(action_id) -> (obs, reward, done, info)  [gym 0.17/0.18
-  4-tuple API], run by a 1-env FFMPVec with autoreset off.  In this gym surface the
+  reset(seed=None) -> obs,  step(action_id or (v, w)) -> (obs, reward, done, info)  [gym
+  0.17/0.18 4-tuple API], run by a 1-env FFMPVec with autoreset off; step takes an action id or a
+  sample of action_space (a continuous command, clipped to the Box).  In this gym surface the
   episode-start distance d0 is per instance (kept on the device), not the module global.
 
 Every compute path goes through libffmp; without it (or without a GPU) calls raise.
@@ -316,14 +317,35 @@ class FFMP(GymEnvBase):
         self._needs_reset = False
         return self._obs()
 
+    @staticmethod
+    def _action_in(action):
+        """step()'s input: a scalar integer -> its action id (IndexError outside 0..27, as indexing
+        RobotAction.cmd); a length-2 float array-like -> the (v, w) command as (1, 2) float64, what
+        action_space (the Box of ffmp.py:29-32) samples — clipped to the Box by the step; NaN raises
+        ValueError.  (A scalar of any other kind is an id, as it always was.)"""
+        arr = np.asarray(action)
+        if arr.ndim >= 1 and arr.size == 2 and arr.dtype.kind == "f":
+            cmd = arr.astype(np.float64).reshape(1, 2)
+            if np.isnan(cmd).any():
+                raise ValueError(f"NaN in the (v, w) command {cmd[0].tolist()}")
+            return None, cmd
+        if arr.ndim >= 1 and arr.size != 1:
+            raise ValueError("action must be an action id (a scalar integer) or a (v, w) command (2 floats), got "
+                             f"{arr.dtype} of shape {arr.shape}")
+        a = int(arr.reshape(()).item()) if arr.ndim >= 1 else int(action)
+        if not 0 <= a < 28:
+            raise IndexError(f"action id {a} out of range 0..27 (RobotAction.cmd has 28 entries)")
+        return a, None
+
     def step(self, action):
         if self._needs_reset:
             raise RuntimeError("call reset() before step() (and after an episode ends)")
-        a = int(action)
-        if not 0 <= a < 28:
-            raise IndexError(f"action id {a} out of range 0..27 (RobotAction.cmd has 28 entries)")
+        a, cmd = self._action_in(action)
         v = self._vec
-        v.step(torch.tensor([a], dtype=torch.int64, device=v.device))
+        if cmd is not None:
+            v.step(torch.as_tensor(cmd, device=v.device))
+        else:
+            v.step(torch.tensor([a], dtype=torch.int64, device=v.device))
         reward = float(v.reward[0].item())
         done = bool(v.done[0].item())
         info = {"is_goal": bool(v.is_goal[0].item()), "collision": bool(v.collision[0].item()),

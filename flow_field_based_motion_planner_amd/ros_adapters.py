@@ -15,7 +15,10 @@ conversions keep the reference's exact semantics:
   pose_array_callback (:126-132)     pose_array_to_start_goal: poses[0], poses[1]
   relative_goal_calculator           relative_goal: [sqrt(dx^2 + dy^2), pi_to_pi(atan2(dy, dx)
     (:167-180)                       - yaw)] in float64, the `relative_goal_info` rewarder2 takes
-  cmd_vel_publisher (:134-143)       action_to_twist: RobotAction.cmd[a] -> linear.x, angular.z
+  cmd_vel_publisher (:134-143)       action_to_twist: RobotAction.cmd[a] -> linear.x, angular.z;
+                                     command_to_twist: a continuous (v, w) -> the same Twist;
+                                     twist_to_command: the way back, a /cmd_vel Twist -> (v, w)
+                                     for FFMPVec.step / FFMP.step
 
 and the other direction, env -> messages: lidar_to_ranges, frame_to_image, pose_to_odometry.
 Host-side (numpy): a bridge talks to one robot at a time.
@@ -118,6 +121,18 @@ def action_to_twist(action: int) -> Msg:
     """cmd_vel_publisher(commander(a)) (train.py:134-143, :668-673)."""
     v, w = action_table()[int(action)]
     return Msg(linear={"x": v, "y": 0.0, "z": 0.0}, angular={"x": 0.0, "y": 0.0, "z": w})
+
+
+def command_to_twist(v: float, w: float) -> Msg:
+    """cmd_vel_publisher (train.py:134-143) for a continuous command: linear.x = v, angular.z = w.
+    command_to_twist(*action_table()[a]) is action_to_twist(a), field for field."""
+    return Msg(linear={"x": float(v), "y": 0.0, "z": 0.0}, angular={"x": 0.0, "y": 0.0, "z": float(w)})
+
+
+def twist_to_command(msg) -> Tuple[float, float]:
+    """The way back from a /cmd_vel Twist (train.py:134-143 sets only linear.x and angular.z) to the
+    (v, w) command FFMPVec.step / FFMP.step take (clipped there to the action Box, ffmp.py:29-32)."""
+    return float(msg.linear.x), float(msg.angular.z)
 
 
 # ----------------------------------------------------------------------------- env -> messages

@@ -12,6 +12,10 @@ and src/train.py drives Gazebo over ROS instead, train.py:523-693).  One call of
     step == MAX_STEPS -> done                 train.py:607-608  -> truncated
     done -> /episode_manager reset            train.py:611-664  -> auto-reset (Philox)
 
+`actions` is either the N action ids (an integer tensor: commander's table) or N continuous
+(v, w) commands (a floating (N, 2) tensor: the action Box of ffmp.py:29-32, any Twist of
+cmd_vel_publisher, train.py:134-143), clipped to the Box by the env kernel (SPEC a15b).
+
 Observation tensors keep the consumer layout of train.py:44,543-557 with a
 leading N: state_m (N,2,G,G) f32, state_g (N,2), state_v (N,2), state_t (N,1);
 extras: potential (N,G,G), grad (N,2), lidar (N,L).
@@ -1181,14 +1185,42 @@ class FFMPVec:
             raise ValueError(f"expected {self.num_envs} actions, got {a.numel()}")
         return a.contiguous()
 
+    def _commands(self, cmds) -> torch.Tensor:
+        """(N, 2) float64 (v, w) commands on the device, contiguous and 16-byte aligned (the env
+        kernel reads each row as one 16-byte load); float32 is widened exactly."""
+        c = torch.as_tensor(cmds)
+        if not c.is_floating_point() or tuple(c.shape) != (self.num_envs, 2):
+            raise ValueError(f"commands must be a floating tensor of shape ({self.num_envs}, 2), got "
+                             f"{c.dtype} {tuple(c.shape)}")
+        if c.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"commands must be float32 or float64, got {c.dtype}")
+        if c.device != self.device or c.dtype != torch.float64:
+            c = c.to(device=self.device, dtype=torch.float64)
+        c = c.contiguous()
+        if c.data_ptr() % 16:
+            c = c.clone()
+        return c
+
+    def _act_in(self, actions) -> Tuple[torch.Tensor, bool]:
+        """step()'s input dispatch (SPEC a15b): an integer tensor of N elements -> (ids (N,) int64,
+        False), today's path; a floating tensor of shape (N, 2) -> ((N, 2) float64 (v, w) commands,
+        True); anything else raises ValueError."""
+        a = torch.as_tensor(actions)
+        if a.is_floating_point():
+            return self._commands(a), True
+        if a.is_complex():
+            raise ValueError("actions must be integer ids (N,) or floating (v, w) commands (N, 2)")
+        return self._actions(a), False
+
     def step_state(self, actions: torch.Tensor) -> None:
         """Kernel 1 of a step: dynamics, lidar, reward/done, auto-reset, record."""
         self._check_open()
-        a = self._actions(actions)
+        a, is_cmd = self._act_in(actions)
         self._act_keepalive = a
-        _abi.check(self.lib.ffmp_step_state(C.byref(self._cfg_c), self.num_envs, self.env_offset, a.data_ptr(),
-                                            C.byref(self._state_c), C.byref(self._obs_c), C.byref(self._out_c),
-                                            self._stream()), "ffmp_step_state")
+        fn, what = (self.lib.ffmp_step_state_cmd, "ffmp_step_state_cmd") if is_cmd else \
+            (self.lib.ffmp_step_state, "ffmp_step_state")
+        _abi.check(fn(C.byref(self._cfg_c), self.num_envs, self.env_offset, a.data_ptr(), C.byref(self._state_c),
+                      C.byref(self._obs_c), C.byref(self._out_c), self._stream()), what)
 
     def raster(self, mask: Optional[torch.Tensor] = None) -> None:
         """Re-raster the current observation (both frames, potential, flow) from the record."""
@@ -1219,16 +1251,17 @@ class FFMPVec:
     def _step_fused(self, actions, timing: Optional[list] = None) -> None:
         """Env step + raster in one launch (ffmp_step_fused): one block per env."""
         self._check_open()
-        a = self._actions(actions)
+        a, is_cmd = self._act_in(actions)
         self._act_keepalive = a
         full = self._next_window()
         flags = self.fused_flags | (0 if full else _abi.RASTER_NEWEST)
         if timing is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-        _abi.check(self.lib.ffmp_step_fused(C.byref(self._cfg_c), self.num_envs, self.env_offset, a.data_ptr(),
-                                            C.byref(self._state_c), C.byref(self._obs_c), C.byref(self._out_c), flags,
-                                            self._stream()), "ffmp_step_fused")
+        fn, what = (self.lib.ffmp_step_fused_cmd, "ffmp_step_fused_cmd") if is_cmd else \
+            (self.lib.ffmp_step_fused, "ffmp_step_fused")
+        _abi.check(fn(C.byref(self._cfg_c), self.num_envs, self.env_offset, a.data_ptr(), C.byref(self._state_c),
+                      C.byref(self._obs_c), C.byref(self._out_c), flags, self._stream()), what)
         if timing is not None:
             e1.record()
             n = self.num_envs
@@ -1243,17 +1276,19 @@ class FFMPVec:
 
     def _step_pipelined(self, actions, timing) -> None:
         self._check_open()
-        a = self._actions(actions)
+        a, is_cmd = self._act_in(actions)
         self._act_keepalive = a
         main = torch.cuda.current_stream(self.device)
         side = self._side
         self._ev_go.record(main)
         side.wait_event(self._ev_go)
         sp = C.c_void_p(side.cuda_stream)
+        # a slice's inputs start a0 ids (8 B each) or a0 (v, w) rows (16 B each) into the array
+        fn, what, esz = (self.lib.ffmp_step_state_cmd, "ffmp_step_state_cmd", 16) if is_cmd else \
+            (self.lib.ffmp_step_state, "ffmp_step_state", 8)
         for k, (a0, n, st, ob, out, rec) in enumerate(self._slices):
-            _abi.check(self.lib.ffmp_step_state(C.byref(self._cfg_c), n, self.env_offset + a0,
-                                                a.data_ptr() + a0 * 8, C.byref(st), C.byref(ob), C.byref(out), sp),
-                       "ffmp_step_state")
+            _abi.check(fn(C.byref(self._cfg_c), n, self.env_offset + a0, a.data_ptr() + a0 * esz, C.byref(st),
+                          C.byref(ob), C.byref(out), sp), what)
             self._ev_slice[k].record(side)
         # the raster of slice k on the main stream once its env slice is done: the env kernels of the
         # later slices run beside it.  The frame pair slides as in raster_step (ring or contiguous).
@@ -1342,14 +1377,23 @@ class FFMPVec:
             self._graphs = {}
             if getattr(self, "action_buffer", None) is None:
                 self.action_buffer = torch.zeros(self.num_envs, dtype=torch.int64, device=self.device)
+            if getattr(self, "command_buffer", None) is None:
+                self.command_buffer = torch.zeros((self.num_envs, 2), dtype=torch.float64, device=self.device)
 
     action_buffer = None
+    command_buffer = None  # (N, 2) float64: the static (v, w) block of the command steps' graphs
 
     def _step_graph(self, actions) -> None:
-        buf = self.action_buffer
-        if not (isinstance(actions, torch.Tensor) and actions.data_ptr() == buf.data_ptr()):
-            buf.copy_(self._actions(actions), non_blocking=True)
-        key = (self._wpos, self.fused)
+        # ids and commands have a static buffer and graphs of their own: the cache is keyed by the kind
+        if isinstance(actions, torch.Tensor) and actions.data_ptr() == self.command_buffer.data_ptr():
+            buf, kind = self.command_buffer, "cmd"
+        elif isinstance(actions, torch.Tensor) and actions.data_ptr() == self.action_buffer.data_ptr():
+            buf, kind = self.action_buffer, "ids"
+        else:
+            a, is_cmd = self._act_in(actions)
+            buf, kind = (self.command_buffer, "cmd") if is_cmd else (self.action_buffer, "ids")
+            buf.copy_(a, non_blocking=True)
+        key = (self._wpos, self.fused, kind)
         g = self._graphs.get(key)
         if g is None:
             g = torch.cuda.CUDAGraph()
@@ -1391,6 +1435,27 @@ class FFMPVec:
                                                      out.data_ptr(), self._stream()), "ffmp_policy_reactive")
         return out
 
+    def policy_field(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The next (v, w) commands (N, 2) float64 from the current observation, on the device
+        (include/ffmp.h ffmp_policy_field): descend the potential field along its gradient at the
+        robot cell (obs["grad"]) — full speed along the descent direction's heading component, turn
+        towards it, turn on the spot when it points behind.  A scripted controller for closed-loop
+        runs over commands, as policy_reactive is over action ids.  `out`: write into this (N, 2)
+        float64 tensor (e.g. command_buffer) instead of a new one."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before policy_field()")
+        if out is None:
+            out = torch.empty((self.num_envs, 2), dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (self.num_envs, 2) or out.dtype != torch.float64 or not out.is_contiguous() \
+                or out.device != self.device or out.data_ptr() % 16:
+            raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
+                             f"({self.num_envs}, 2) on {self.device}")
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_policy_field(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
+                                                  out.data_ptr(), self._stream()), "ffmp_policy_field")
+        return out
+
     # ------------------------------------------------ HIP graph of whole steps
     def graph_period(self) -> int:
         """Steps after which the frame pair is back on the same ring slots (so one captured
@@ -1401,7 +1466,7 @@ class FFMPVec:
         return self.frame_window - 1 if self.frame_window > 2 else 1
 
     def capture(self, steps: Optional[int] = None, pipelined: Optional[bool] = None,
-                skewed: Optional[bool] = None, policy=None) -> "StepGraph":
+                skewed: Optional[bool] = None, policy=None, commands: bool = False) -> "StepGraph":
         """Capture `steps` consecutive steps (default graph_period(); a multiple of it) into one HIP
         graph (torch.cuda.CUDAGraph: hipGraph on ROCm).  StepGraph.replay(actions) then runs them as
         ONE launch from the host — every kernel of every step, the same launches step() makes, with
@@ -1416,8 +1481,13 @@ class FFMPVec:
         tensor, captured too: each step's actions are computed inside the graph from the previous
         step's observation (the first from the observation before the replay), and replay() takes
         no actions — the device-resident form of train.py:572-577's act-then-publish loop.  Plain
-        two-launch (or one-launch) steps only: the policy reads the raster's frame."""
-        return StepGraph(self, steps, pipelined, skewed, policy)
+        two-launch (or one-launch) steps only: the policy reads the raster's frame.
+        Continuous (v, w) commands (SPEC a15b): policy="field" (policy_field; the static block is
+        (steps, N, 2) float64 and replay() takes no actions), or commands=True for an open loop whose
+        replay(cmds) takes a (steps, N, 2) block.  Command graphs run plain steps: pipelined=True or
+        skewed=True raises ValueError (the skewed launch reads ids a step ahead), and their defaults
+        resolve to off."""
+        return StepGraph(self, steps, pipelined, skewed, policy, commands)
 
     # ------------------------------------------------ gym.vector.VectorEnv surface
     is_vector_env = True
@@ -1433,6 +1503,22 @@ class FFMPVec:
     def action_space(self):
         from ._spaces import MultiDiscrete
         return MultiDiscrete([28] * self.num_envs)
+
+    @property
+    def single_command_space(self):
+        """The (v, w) command step() also takes (SPEC a15b): the reference's action Box
+        [0, -0.6] .. [0.6, 0.6] (ffmp.py:29-32), float32."""
+        from ._spaces import Box
+        from .config import CMD_V, CMD_W
+        return Box(np.array([CMD_V[0], CMD_W[0]], dtype=np.float32),
+                   np.array([CMD_V[-1], CMD_W[-1]], dtype=np.float32), dtype=np.float32)
+
+    @property
+    def command_space(self):
+        from ._spaces import Box
+        one = self.single_command_space
+        return Box(np.broadcast_to(one.low, (self.num_envs, 2)), np.broadcast_to(one.high, (self.num_envs, 2)),
+                   dtype=np.float32)
 
     def _obs_space(self, lead):
         """Keys/dtypes of the train.py consumer contract (train.py:543-557), bounds per key."""
@@ -1498,6 +1584,7 @@ class FFMPVec:
         torch.cuda.synchronize(self.device)
         self._graphs = None  # their kernels' arguments point into the buffers freed below
         self.action_buffer = None
+        self.command_buffer = None
         for name, _, _ in self._buffer_specs():
             setattr(self, name, None)
         # the launch structs hold raw device pointers into the freed buffers
@@ -1524,11 +1611,16 @@ class FFMPVec:
 
     # ------------------------------------------------------------ utilities
     def check_errors(self) -> None:
-        """Raise if any step saw an action id outside 0..27 (it was run as action 3)."""
+        """Raise if any step saw an action id outside 0..27 (bit 1; it was run as action 3) or a NaN
+        command (bit 2; it was run as (0, 0)).  Clears the bits."""
         v = int(self.err.item())
         if v:
             self.err.zero_()
-            raise ValueError(f"invalid action id(s) passed to FFMPVec.step (error bits {v:#x})")
+            if v == 1:  # the ids path alone: its message as it always was
+                raise ValueError(f"invalid action id(s) passed to FFMPVec.step (error bits {v:#x})")
+            what = ([] if not v & 1 else ["invalid action id(s)"]) + ([] if not v & 2 else ["NaN command(s)"])
+            raise ValueError(f"{' and '.join(what) or 'errors'} passed to FFMPVec.step (error bits {v:#x}; "
+                             "bit 2: NaN command)")
 
     # simulator state, then the per-env observations and outputs the env kernel wrote (the planes
     # are re-rastered from the record on load)
@@ -1646,13 +1738,23 @@ class StepGraph:
         return blocks <= torch.cuda.get_device_properties(env.device).multi_processor_count
 
     def __init__(self, env: FFMPVec, steps: Optional[int] = None, pipelined: Optional[bool] = None,
-                 skewed: Optional[bool] = None, policy=None):
+                 skewed: Optional[bool] = None, policy=None, commands: bool = False):
         env._check_open()
         if policy is not None:
             if pipelined or skewed:
                 raise ValueError("a closed-loop graph (policy) runs plain steps: the policy reads each raster's frame")
-            if policy != "reactive" and not callable(policy):
-                raise ValueError("policy must be 'reactive' or a callable env -> (N,) int64 tensor")
+            if policy not in ("reactive", "field") and not callable(policy):
+                raise ValueError("policy must be 'reactive', 'field' or a callable env -> (N,) int64 tensor")
+            pipelined = skewed = False
+        # (v, w) commands instead of ids: the field follower's closed loop, or an open loop (commands=True)
+        self.commands = bool(commands) or policy == "field"
+        if self.commands:
+            if callable(policy):
+                raise ValueError("commands=True takes policy='field' or no policy (a callable policy returns ids)")
+            if policy == "reactive":
+                raise ValueError("policy='reactive' computes action ids, not commands")
+            if pipelined or skewed:
+                raise ValueError("a command graph runs plain steps: the pipelined and skewed forms read action ids")
             pipelined = skewed = False
         self.policy = policy
         if env._needs_reset:
@@ -1667,7 +1769,9 @@ class StepGraph:
         # any other count is replayable once the frame position is back at the capture's
         self.chainable = k % per == 0
         self.env, self.steps = env, k
-        self.actions = torch.zeros((k, env.num_envs), dtype=torch.int64, device=env.device)
+        # the static block the captured steps read: ids (k, N) int64, or commands (k, N, 2) float64
+        self.actions = torch.zeros((k, env.num_envs, 2), dtype=torch.float64, device=env.device) if self.commands \
+            else torch.zeros((k, env.num_envs), dtype=torch.int64, device=env.device)
         can_pipe = not env.fused and k % 2 == 0
         if pipelined is None:
             pipelined = can_pipe and self.PIPELINE_DEFAULT
@@ -1721,6 +1825,8 @@ class StepGraph:
         """Closed loop: step i's actions from the current observation, into the static block."""
         if self.policy == "reactive":
             self.env.policy_reactive(out=self.actions[i])
+        elif self.policy == "field":
+            self.env.policy_field(out=self.actions[i])
         else:
             a = self.policy(self.env)
             if not (isinstance(a, torch.Tensor) and a.numel() == self.env.num_envs):
@@ -1772,7 +1878,8 @@ class StepGraph:
         env.raster_step()
 
     def replay(self, actions: Optional[torch.Tensor] = None) -> None:
-        """Run the captured steps; actions (steps, N) int64 (None: the block the last replay used)."""
+        """Run the captured steps; actions (steps, N) int64 — or, for a commands=True graph,
+        (steps, N, 2) float32 / float64 (v, w) commands — (None: the block the last replay used)."""
         env = self.env
         env._check_open()
         if env._needs_reset:
@@ -1785,6 +1892,8 @@ class StepGraph:
             a = torch.as_tensor(actions)
             if a.shape != self.actions.shape:
                 raise ValueError(f"actions must have shape {tuple(self.actions.shape)}")
+            if self.commands and a.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"commands must be float32 or float64, got {a.dtype}")
             self.actions.copy_(a, non_blocking=True)
         with torch.cuda.device(env.device):
             self.graph.replay()

@@ -18,6 +18,10 @@
  *   ffmp_step, ffmp_step_fused -> one iteration of src/train.py:523-693 with Gazebo
  *                          (/cmd_vel integration), /bev_* rasterisers and
  *                          rewarder2 (src/gym_ffmp/envs/ffmp.py:179-188) in-GPU
+ *   ffmp_step_state_cmd, ffmp_step_fused_cmd, ffmp_step_cmd -> the same iteration driven by a
+ *                          continuous (v, w) command: the action Box of
+ *                          src/gym_ffmp/envs/ffmp.py:29-32 published as a Twist by
+ *                          cmd_vel_publisher (src/train.py:134-143)
  *   ffmp_ring_*, ffmp_dlpack -> storage of make_temporal_maps' 2-frame stack
  *                          (src/train.py:474-486) kept in place (optional helper)
  *   ffmp_temporal_maps  -> make_temporal_maps over INPUT_CHANNELS = k mono frames
@@ -47,7 +51,7 @@
 extern "C" {
 #endif
 
-#define FFMP_ABI_VERSION 8  /* 8: ffmp_step_skewed_check, ffmp_policy_reactive, ffmp_ring_va_reserved */
+#define FFMP_ABI_VERSION 9  /* 9: ffmp_step_state_cmd, ffmp_step_fused_cmd, ffmp_step_cmd, ffmp_policy_field */
 #define FFMP_MAX_OBST 64     /* K  */
 #define FFMP_MAX_FOOT 128    /* footprint cells */
 #define FFMP_MAX_BEAMS 1024  /* L  */
@@ -117,7 +121,7 @@ typedef struct ffmp_state {
   int32_t* t;       /* (N)   steps since episode start               */
   int32_t* episode; /* (N)   episode counter (RNG key part)          */
   float* record;    /* (N, FFMP_REC_HDR + 12K) raster record */
-  uint32_t* err;    /* (1)   sticky error bits (bit0: bad action id) */
+  uint32_t* err;    /* (1)   sticky error bits (value 1: bad action id, value 2: NaN command) */
   /* Optional (NULL = not written): the post-step state of every env BEFORE auto-reset, i.e. what
    * the reference loop observes on the iteration that ends an episode (train.py:543-557) —
    * consumers that store transitions (a replay memory) need it for done envs. Written by
@@ -317,6 +321,41 @@ int ffmp_policy_reactive(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs
 int ffmp_step(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset,
               const int64_t* action, ffmp_state_t* state, ffmp_obs_t* obs,
               ffmp_out_t* out, void* stream);
+
+/* Continuous velocity commands (ABI 9) — the reference's action space is the Box
+ * [0, -0.6] .. [0.6, 0.6] of (v, w) (src/gym_ffmp/envs/ffmp.py:29-32) and cmd_vel_publisher sends
+ * any such Twist (src/train.py:134-143); the 28 action ids are one table over it.  cmd: (n, 2)
+ * float64 DEVICE memory, row e = {v, w} of env e, 16-byte aligned (read as one 16-byte load per env).
+ * Per env:
+ *   v or w NaN           -> the env runs (0.0, 0.0) and error value 2 is ORed into *state->err
+ *   v = v < 0.0 ? 0.0 : (v > 0.6 ? 0.6 : v)        (the bounds are cmd[0] and cmd[27]; +-inf clips,
+ *   w = w < -0.6 ? -0.6 : (w > 0.6 ? 0.6 : w)       -0.0 passes through)
+ * and the step from the unicycle integrator on is that of the action-id entry points: a command
+ * equal to the float64 table entry of action id a gives the bits ffmp_step_state gives for a.
+ * ffmp_step_state_cmd / ffmp_step_fused_cmd / ffmp_step_cmd are ffmp_step_state / ffmp_step_fused /
+ * ffmp_step with that command source (every other argument as there).  cmd NULL or not 16-byte
+ * aligned: FFMP_E_ARG; n == 0: nothing is launched.  (ffmp_step_skewed takes ids only: it needs the
+ * actions a step ahead, which a closed loop over commands never has.) */
+int ffmp_step_state_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd,
+                        ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, void* stream);
+int ffmp_step_fused_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd,
+                        ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, int32_t flags, void* stream);
+int ffmp_step_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd,
+                  ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, void* stream);
+
+/* A scripted field follower — no reference counterpart (the reference's commands come from its
+ * Q-network through cmd_vel_publisher, src/train.py:134-143, inside the Box of
+ * src/gym_ffmp/envs/ffmp.py:29-32) — that descends the potential field: per env, from obs->grad
+ * (float32, ego frame, x = heading), in float64 and in this order:
+ *   gx, gy = grad[0], grad[1];  m2 = gx*gx + gy*gy
+ *   m2 not > 0, or not finite:  cmd = (0, 0)
+ *   else  m = sqrt(m2);  dx = -gx / m;  dy = -gy / m          (unit descent direction)
+ *         w = dy / cfg->dt, then w < -0.6 ? -0.6 : (w > 0.6 ? 0.6 : w)
+ *         if dx < 0:  w = dy >= 0 ? 0.6 : -0.6                 (descent points behind: turn on the spot)
+ *         v = 0.6 * (dx > 0 ? dx : 0.0)
+ * cmd: (n, 2) float64 device memory, 16-byte aligned — what the *_cmd steps read.  obs->grad or cmd
+ * NULL, cmd misaligned: FFMP_E_ARG; n == 0: nothing is launched.  One lane per env. */
+int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, double* cmd, void* stream);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
