@@ -120,6 +120,9 @@ _SIGS = {
     "ffmp_step_cmd": (C.c_int, [C.POINTER(CfgT), _I64, _I64, _P, C.POINTER(StateT), C.POINTER(ObsT),
                                 C.POINTER(OutT), _P]),
     "ffmp_policy_field": (C.c_int, [C.POINTER(CfgT), _I64, C.POINTER(ObsT), _P, _P]),
+    # injected episodes (an addition within ABI 9): ffmp_reset with the episode from (n, .) float64 arrays
+    "ffmp_set_scenario": (C.c_int, [C.POINTER(CfgT), _I64, _I64, _P, _P, _P, _P, _P, _P, C.POINTER(StateT),
+                                    C.POINTER(ObsT), _P]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

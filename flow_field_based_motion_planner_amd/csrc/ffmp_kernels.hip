@@ -131,6 +131,19 @@ Tuning& tuning() {
 
 constexpr int kEnvMode_Step = 0;
 constexpr int kEnvMode_Reset = 1;
+constexpr int kEnvMode_Scenario = 2;  // a reset whose episode is the caller's (ffmp_set_scenario, SPEC a16b)
+
+// The caller's arrays of an injected episode (ffmp_set_scenario), (n, .) float64 device memory;
+// obst / obst_r may be NULL with K = 0, episode NULL: the counter moves on by one.
+struct ScenarioSrc {
+  const double* pose;      // (n, 3) x, y, yaw
+  const double* goal;      // (n, 2)
+  const double* obst;      // (n, K, 4) x, y, vx, vy
+  const double* obst_r;    // (n, K)
+  const int32_t* episode;  // (n) or NULL
+};
+// pi_to_pi is the reference's loop, one turn per trip: an injected yaw beyond this is a bad scenario
+constexpr double kScenarioYawMax = 1024.0;
 
 __host__ __device__ inline int64_t rec_stride(int K) { return FFMP_REC_HDR + 12 * (int64_t)K; }
 
@@ -264,6 +277,11 @@ using act_t = std::conditional_t<CMD, double2, int64_t>;
 // id (int64, the 28-entry table); true: action[e] is the env's continuous (v, w) command (two
 // float64, one 16-byte load), clipped to the table's bounds.  Everything after the command is the
 // same code, so a command equal to a table entry steps bit-identically to that entry's id.
+// MODE kEnvMode_Scenario (SPEC a16b): the reset with its Episode and discs read from the caller's
+// arrays in place of the Philox sampler — this mode has no actions, and `action` carries the
+// ScenarioSrc's address (so env_group's signature, which its lambdas' symbols spell out, is what it
+// was); an env with a non-finite word, a negative radius or |yaw| > kScenarioYawMax is left as it was
+// (nothing is written before the test) and error value 4 is ORed into *st.err.
 template <int MODE, int LPE, int BCH = FFMP_BEAM_CHUNK, bool DL = false, int DPL = 1, bool CMD = false>
 FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, int64_t env_offset,
                                                        const act_t<CMD>* __restrict__ action, int32_t initial,
@@ -307,7 +325,7 @@ FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, in
   double c0 = 0.0, s0 = 0.0;
   double vlin = 0.0, vang = 0.0;
   float t_obs = 0.0f;
-  bool reset_now = (MODE == kEnvMode_Reset);
+  bool reset_now = (MODE != kEnvMode_Step);
 
   if (MODE == kEnvMode_Step) {
     // ---- action -> (v, w) (train.py:668-673 -> Gazebo /cmd_vel) ----
@@ -525,13 +543,39 @@ FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, in
   FFMP_ENV_STAMP(4);
   if (reset_now) {
     // ---- episode reset (the external /episode_manager; train.py:559-566) ----
-    episode = (MODE == kEnvMode_Reset && initial) ? 0 : episode + 1;
-    const Episode ep = sample_episode(cfg, genv, episode);
-    x1 = ep.x; y1 = ep.y; yaw1 = ep.yaw; gx = ep.gx; gy = ep.gy;
-    wave_sync();  // all lanes done reading the terminal-state LDS arrays
+    if constexpr (MODE == kEnvMode_Scenario) {
+      // ---- the caller's episode (SPEC a16b): validated before anything of the env is written ----
+      const ScenarioSrc* scn = reinterpret_cast<const ScenarioSrc*>(action);
+      auto finite = [](double v) { return v - v == 0.0; };
+      const double* sp = scn->pose + e * 3;
+      const double* sg = scn->goal + e * 2;
+      const double sx = sp[0], sy = sp[1], syaw = sp[2], sgx = sg[0], sgy = sg[1];
+      bool bad = !(finite(sx) && finite(sy) && finite(sgx) && finite(sgy) && fabs(syaw) <= kScenarioYawMax);
 #pragma unroll
-    for (int j = 0; j < DPL; ++j)
-      if (has_obst[j]) my[j] = sample_obstacle(cfg, genv, episode, lane + j * LPE, ep);
+      for (int j = 0; j < DPL; ++j)
+        if (has_obst[j]) {
+          const int k = lane + j * LPE;
+          const double* p = scn->obst + (e * K + k) * 4;
+          my[j].x = p[0]; my[j].y = p[1]; my[j].vx = p[2]; my[j].vy = p[3];
+          my[j].r = scn->obst_r[e * K + k];
+          bad = bad || !(finite(my[j].x) && finite(my[j].y) && finite(my[j].vx) && finite(my[j].vy) &&
+                         finite(my[j].r) && my[j].r >= 0.0);
+        }
+      if (group_ballot(bad, LPE) != 0) {
+        if (lane == 0) atomicOr(st.err, 4u);
+        return;
+      }
+      episode = scn->episode ? scn->episode[e] : episode + 1;
+      x1 = sx; y1 = sy; yaw1 = pi_to_pi(syaw); gx = sgx; gy = sgy;
+    } else {
+      episode = (MODE == kEnvMode_Reset && initial) ? 0 : episode + 1;
+      const Episode ep = sample_episode(cfg, genv, episode);
+      x1 = ep.x; y1 = ep.y; yaw1 = ep.yaw; gx = ep.gx; gy = ep.gy;
+      wave_sync();  // all lanes done reading the terminal-state LDS arrays
+#pragma unroll
+      for (int j = 0; j < DPL; ++j)
+        if (has_obst[j]) my[j] = sample_obstacle(cfg, genv, episode, lane + j * LPE, ep);
+    }
     c1 = cos(yaw1); s1 = sin(yaw1);
 #pragma unroll
     for (int j = 0; j < DPL; ++j)
@@ -605,6 +649,33 @@ __global__ __launch_bounds__(64 * kEnvWaves) FFMP_ENV_OCC void env_kernel(ffmp_c
                        s_oxa[wv] + g0, s_oya[wv] + g0, s_ora[wv] + g0, s_orra[wv] + g0,
                        s_ecura[wv] + g0, s_epreva[wv] + g0, s_foota[wv], nullptr, nullptr,
                        s_keys + ((size_t)wv * EPW + grp) * cfg.n_beams, s_prefa[wv] + g0, s_loa[wv] + g0);
+}
+
+// env_kernel's reset with the episode from the caller's arrays (env_group's kEnvMode_Scenario): the
+// same block shape, LDS slices and lane layouts, a kernel of its own so that env_kernel's
+// instantiations stay what they were.
+template <int kEnvWaves, int LPE, int DPL>
+__global__ __launch_bounds__(64 * kEnvWaves) void scenario_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
+                                                                  const uint8_t* __restrict__ mask, ScenarioSrc scn,
+                                                                  ffmp_state_t st, ffmp_obs_t ob) {
+  constexpr int EPW = 64 / LPE;
+  constexpr int DS = 64 * DPL;
+  __shared__ double s_oxa[kEnvWaves][DS], s_oya[kEnvWaves][DS], s_ora[kEnvWaves][DS], s_orra[kEnvWaves][DS];
+  __shared__ float4 s_ecura[kEnvWaves][DS], s_epreva[kEnvWaves][DS];
+  extern __shared__ uint32_t s_keys[];
+  __shared__ int s_prefa[kEnvWaves][DS], s_loa[kEnvWaves][DS];
+
+  const int wv = threadIdx.x >> 6;
+  const int grp = (threadIdx.x & 63) / LPE;
+  const int64_t e = ((int64_t)blockIdx.x * kEnvWaves + wv) * EPW + grp;
+  const int lane = threadIdx.x & (LPE - 1);
+  if (e >= n) return;
+  if (mask && !mask[e]) return;
+  const int g0 = grp * LPE * DPL;
+  env_group<kEnvMode_Scenario, LPE, FFMP_BEAM_CHUNK, true, DPL, false>(
+      cfg, env_offset, reinterpret_cast<const int64_t*>(&scn), 0, st, ob, ffmp_out_t{}, e, lane, s_oxa[wv] + g0,
+      s_oya[wv] + g0, s_ora[wv] + g0, s_orra[wv] + g0, s_ecura[wv] + g0, s_epreva[wv] + g0, nullptr, nullptr, nullptr,
+      s_keys + ((size_t)wv * EPW + grp) * cfg.n_beams, s_prefa[wv] + g0, s_loa[wv] + g0);
 }
 
 // ============================================================================
@@ -1518,18 +1589,24 @@ template <int MODE, int W, int LPE, int DPL, bool CMD>
 bool launch_env_t(const ffmp_cfg_t& cfg, int64_t n, int64_t env_offset, const void* action, const uint8_t* mask,
                   int32_t initial, const ffmp_state_t& st, const ffmp_obs_t& ob, const ffmp_out_t& o,
                   hipStream_t s) {
+  // kEnvMode_Scenario: `action` is the host's ScenarioSrc and the kernel is scenario_kernel
   static const size_t static_lds = [] {
     hipFuncAttributes a{};
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&env_kernel<MODE, W, LPE, DPL, CMD>)) == hipSuccess
-               ? (size_t)a.sharedSizeBytes
-               : (size_t)0;
+    const void* fn;
+    if constexpr (MODE == kEnvMode_Scenario) fn = reinterpret_cast<const void*>(&scenario_kernel<W, LPE, DPL>);
+    else fn = reinterpret_cast<const void*>(&env_kernel<MODE, W, LPE, DPL, CMD>);
+    return hipFuncGetAttributes(&a, fn) == hipSuccess ? (size_t)a.sharedSizeBytes : (size_t)0;
   }();
   const int64_t per_block = (int64_t)W * (64 / LPE);
   const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
   const size_t lds = (size_t)W * (64 / LPE) * (size_t)cfg.n_beams * sizeof(uint32_t);  // trace_discs' beam minima
   if (static_lds + lds > device_lds_limit()) return false;
-  hipLaunchKernelGGL((env_kernel<MODE, W, LPE, DPL, CMD>), dim3(blocks), dim3(64 * W), lds, s, cfg, n, env_offset,
-                     static_cast<const act_t<CMD>*>(action), mask, initial, st, ob, o);
+  if constexpr (MODE == kEnvMode_Scenario)
+    hipLaunchKernelGGL((scenario_kernel<W, LPE, DPL>), dim3(blocks), dim3(64 * W), lds, s, cfg, n, env_offset, mask,
+                       *static_cast<const ScenarioSrc*>(action), st, ob);
+  else
+    hipLaunchKernelGGL((env_kernel<MODE, W, LPE, DPL, CMD>), dim3(blocks), dim3(64 * W), lds, s, cfg, n, env_offset,
+                       static_cast<const act_t<CMD>*>(action), mask, initial, st, ob, o);
   return true;
 }
 
@@ -1555,6 +1632,9 @@ bool launch_env_lpe(int mode, bool cmd, int lpe, int dpl, const ffmp_cfg_t& cfg,
     return launch_env_mode<kEnvMode_Step, W, true>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
   if (mode == kEnvMode_Step)
     return launch_env_mode<kEnvMode_Step, W, false>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
+  if (mode == kEnvMode_Scenario)  // `action` is the ScenarioSrc (ffmp_set_scenario)
+    return launch_env_mode<kEnvMode_Scenario, W, false>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o,
+                                                        s);
   return launch_env_mode<kEnvMode_Reset, W, false>(lpe, dpl, cfg, n, env_offset, action, mask, initial, st, ob, o, s);
 }
 
@@ -1910,12 +1990,25 @@ static int launch_env(int mode, bool cmd, const ffmp_cfg_t* cfg, int64_t n, int6
   if (!ok)
     return fail(FFMP_E_ARG, "no env_kernel layout fits the %zu B of LDS a block may use (K = %d, L = %d)",
                 device_lds_limit(), cfg->n_obst, cfg->n_beams);
-  return check_launch(mode != kEnvMode_Step ? "ffmp_reset" : cmd ? "ffmp_step_state_cmd" : "ffmp_step_state");
+  return check_launch(mode == kEnvMode_Scenario ? "ffmp_set_scenario"
+                      : mode != kEnvMode_Step   ? "ffmp_reset"
+                      : cmd                     ? "ffmp_step_state_cmd"
+                                                : "ffmp_step_state");
 }
 
 int ffmp_reset(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const uint8_t* mask,
                int32_t initial, ffmp_state_t* state, ffmp_obs_t* obs, void* stream) {
   return launch_env(kEnvMode_Reset, false, cfg, n, env_offset, nullptr, mask, initial, state, obs, nullptr, stream);
+}
+
+int ffmp_set_scenario(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const uint8_t* mask, const double* pose,
+                      const double* goal, const double* obst, const double* obst_r, const int32_t* episode,
+                      ffmp_state_t* state, ffmp_obs_t* obs, void* stream) {
+  if (!pose || !goal) return fail(FFMP_E_ARG, "scenario pose/goal is NULL");
+  if (cfg && cfg->n_obst > 0 && (!obst || !obst_r))
+    return fail(FFMP_E_ARG, "scenario obst/obst_r is NULL with n_obst > 0");
+  const ScenarioSrc scn{pose, goal, obst, obst_r, episode};
+  return launch_env(kEnvMode_Scenario, false, cfg, n, env_offset, &scn, mask, 0, state, obs, nullptr, stream);
 }
 
 int ffmp_step_state(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action,

@@ -21,7 +21,8 @@ buffer, one copy in, the kernel, one copy out, the stream synchronized; the foot
 New (the reference's reset is commented out, ffmp.py:77-83, and it has no step):
   reset(seed=None) -> obs,  step(action_id or (v, w)) -> (obs, reward, done, info)  [gym
   0.17/0.18 4-tuple API], run by a 1-env FFMPVec with autoreset off; step takes an action id or a
-  sample of action_space (a continuous command, clipped to the Box).  In this gym surface the
+  sample of action_space (a continuous command, clipped to the Box); reset(options={"scenario":
+  {...}}) starts from the caller's start / goal / discs (FFMPVec.set_scenarios).  In this gym surface the
   episode-start distance d0 is per instance (kept on the device), not the module global.
 
 Every compute path goes through libffmp; without it (or without a GPU) calls raise.
@@ -311,9 +312,22 @@ class FFMP(GymEnvBase):
             d["lidar"] = v.lidar[0].cpu().numpy()
         return d
 
-    def reset(self, seed: Optional[int] = None):
+    def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
+        """options={"scenario": {...}}: after the reset, put the env into the caller's episode — the
+        keyword arguments of FFMPVec.set_scenarios with one row each (pose (1, 3), goal (1, 2), obst
+        (1, K, 4), obst_r (1, K), optionally episode (1,)), e.g. what
+        ros_adapters.pose_array_to_scenario builds.  A bad scenario raises ValueError."""
+        scenario = None
+        if options is not None:
+            unknown = set(options) - {"scenario"}
+            if unknown:
+                raise ValueError(f"unknown reset option(s) {sorted(unknown)}; known: 'scenario'")
+            scenario = options.get("scenario")
         v = self._vec_env()
         v.reset(seed=seed)
+        if scenario is not None:
+            v.set_scenarios(**scenario)
+            v.check_errors()
         self._needs_reset = False
         return self._obs()
 

@@ -12,7 +12,9 @@ conversions keep the reference's exact semantics:
     (:116-121)                       raw 0..255 (kornia.image_to_tensor(keepdim=True).float())
   robot_position_extractor           odometry_to_pose: (x, y, yaw) with yaw from the quaternion
     (:157-165)                       (tf euler_from_quaternion, axes 'sxyz'), stamp -> seconds
-  pose_array_callback (:126-132)     pose_array_to_start_goal: poses[0], poses[1]
+  pose_array_callback (:126-132)     pose_array_to_start_goal: poses[0], poses[1];
+                                     pose_array_to_scenario: that start / goal plus the discs as
+                                     the arrays FFMPVec.set_scenarios / FFMP.reset(options=) take
   relative_goal_calculator           relative_goal: [sqrt(dx^2 + dy^2), pi_to_pi(atan2(dy, dx)
     (:167-180)                       - yaw)] in float64, the `relative_goal_info` rewarder2 takes
   cmd_vel_publisher (:134-143)       action_to_twist: RobotAction.cmd[a] -> linear.x, angular.z;
@@ -96,6 +98,39 @@ def pose_array_to_start_goal(msg) -> Tuple[Tuple[float, float], Tuple[float, flo
     """pose_array_callback (train.py:126-132): start = poses[0], goal = poses[1] (x, y)."""
     s, g = msg.poses[0].position, msg.poses[1].position
     return (float(s.x), float(s.y)), (float(g.x), float(g.y))
+
+
+def pose_array_to_scenario(start, goal, obstacles=(), cfg=None) -> dict:
+    """An episode arriving from outside — the start and goal of /start_goal_points
+    (pose_array_callback, train.py:113-132; e.g. pose_array_to_start_goal's pair) plus the discs the
+    simulator holds — as the arrays FFMPVec.set_scenarios / FFMP.reset(options={"scenario": ...})
+    take, one row each: pose (1, 3), goal (1, 2), obst (1, K, 4), obst_r (1, K), float64.
+    start: (x, y) or (x, y, yaw) (yaw 0.0 if absent); goal: (x, y); obstacles: a sequence of
+    (x, y, r) or (x, y, r, vx, vy).  cfg (an FFMPConfig): K = cfg.n_obst, the rest padded with parked
+    discs as the sampler's (r = 0 at (3 W, 3 W)), ValueError if more than K are given; without cfg,
+    K = len(obstacles)."""
+    s = [float(v) for v in start]
+    g = [float(v) for v in goal]
+    if len(s) not in (2, 3) or len(g) != 2:
+        raise ValueError("start must be (x, y) or (x, y, yaw) and goal (x, y)")
+    discs = []
+    for o in obstacles:
+        o = [float(v) for v in o]
+        if len(o) not in (3, 5):
+            raise ValueError("an obstacle must be (x, y, r) or (x, y, r, vx, vy)")
+        discs.append(o + [0.0, 0.0] if len(o) == 3 else o)
+    K = len(discs) if cfg is None else int(cfg.n_obst)
+    if len(discs) > K:
+        raise ValueError(f"{len(discs)} obstacles given, the config holds n_obst = {K}")
+    park = 0.0 if cfg is None else 3.0 * float(cfg.W)
+    obst = np.zeros((1, K, 4), dtype=np.float64)
+    obst[0, :, 0:2] = park
+    obst_r = np.zeros((1, K), dtype=np.float64)
+    for k, (x, y, r, vx, vy) in enumerate(discs):
+        obst[0, k] = (x, y, vx, vy)
+        obst_r[0, k] = r
+    return {"pose": np.array([[s[0], s[1], s[2] if len(s) == 3 else 0.0]], dtype=np.float64),
+            "goal": np.array([g], dtype=np.float64), "obst": obst, "obst_r": obst_r}
 
 
 def _wrap_pi(a: float) -> float:

@@ -43,6 +43,42 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def scenario_tensors(num_envs: int, n_obst: int, pose, goal, obst=None, obst_r=None, episode=None,
+                     device="cpu") -> Dict[str, Optional[torch.Tensor]]:
+    """set_scenarios' host-side argument check (no GPU needed with device="cpu"): the arrays as
+    contiguous float64 tensors on `device` — pose (N, 3), goal (N, 2), obst (N, K, 4), obst_r (N, K)
+    (both None where K == 0) — and episode (N,) int32 or None.  Tensors or arrays, float32 (widened
+    exactly) or float64, from any device; a wrong shape or a dtype of another kind is a ValueError."""
+    N, K = int(num_envs), int(n_obst)
+
+    def f64(name, x, shape):
+        t = torch.as_tensor(x)
+        if not t.is_floating_point() or t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{name} must be float32 or float64, got {t.dtype}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {tuple(t.shape)}")
+        return t.to(device=device, dtype=torch.float64).contiguous()
+
+    out = {"pose": f64("pose", pose, (N, 3)), "goal": f64("goal", goal, (N, 2)), "obst": None, "obst_r": None,
+           "episode": None}
+    if K > 0:
+        if obst is None or obst_r is None:
+            raise ValueError(f"obst and obst_r are needed with n_obst = {K}")
+        out["obst"], out["obst_r"] = f64("obst", obst, (N, K, 4)), f64("obst_r", obst_r, (N, K))
+    else:
+        for name, x, shape in (("obst", obst, (N, 0, 4)), ("obst_r", obst_r, (N, 0))):
+            if x is not None and tuple(torch.as_tensor(x).shape) != shape:
+                raise ValueError(f"{name} must have shape {shape} with n_obst = 0, got {tuple(torch.as_tensor(x).shape)}")
+    if episode is not None:
+        ep = torch.as_tensor(episode)
+        if ep.is_floating_point() or ep.is_complex() or ep.dtype == torch.bool:
+            raise ValueError(f"episode must be an integer tensor, got {ep.dtype}")
+        if tuple(ep.shape) != (N,):
+            raise ValueError(f"episode must have shape {(N,)}, got {tuple(ep.shape)}")
+        out["episode"] = ep.to(device=device, dtype=torch.int32).contiguous()
+    return out
+
+
 class FFMPVec:
     """Batched FFMP env on one GPU.
 
@@ -1176,6 +1212,52 @@ class FFMPVec:
         self._needs_reset = False
         return self._obs_out(copy)
 
+    # ------------------------------------------------ injected episodes (SPEC a16b)
+    def set_scenarios(self, pose, goal, obst=None, obst_r=None, mask=None, episode=None, copy: bool = False):
+        """Put the masked envs (mask None: all) into the caller's episodes (include/ffmp.h
+        ffmp_set_scenario): the masked reset with the sampled start / goal / discs replaced by
+        `pose` (N, 3) x, y, yaw, `goal` (N, 2), `obst` (N, K, 4) x, y, vx, vy and `obst_r` (N, K)
+        — tensors or arrays, float32 (widened exactly) or float64, on any device; with K == 0 the
+        obst arguments may be omitted.  `episode` (N,) integers: the envs' new episode counters (None:
+        episode + 1, as a masked reset) — a later auto-reset samples (seed, episode + 1, env).  An env
+        with a non-finite word, a negative radius or |yaw| > 1024 stays as it was and sets error bit
+        4 (check_errors: "bad scenario").  The frame window does not move (so step graphs captured
+        before stay valid); needs a prior reset().  Returns the observation, like reset()."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before set_scenarios()")
+        sc = scenario_tensors(self.num_envs, self.cfg.n_obst, pose, goal, obst, obst_r, episode, self.device)
+        with torch.cuda.device(self.device):
+            m = None
+            if mask is not None:
+                m = torch.as_tensor(mask).to(device=self.device, dtype=torch.bool).contiguous().view(torch.uint8)
+                if m.numel() != self.num_envs:
+                    raise ValueError("mask must have num_envs elements")
+            _abi.check(self.lib.ffmp_set_scenario(C.byref(self._cfg_c), self.num_envs, self.env_offset, _ptr(m),
+                                                  sc["pose"].data_ptr(), sc["goal"].data_ptr(), _ptr(sc["obst"]),
+                                                  _ptr(sc["obst_r"]), _ptr(sc["episode"]), C.byref(self._state_c),
+                                                  C.byref(self._obs_c), self._stream()), "ffmp_set_scenario")
+            self._raster_launch(True, m)
+            self._mask_keepalive, self._scenario_keepalive = m, sc
+            self._bev_push(advance=False)
+        return self._obs_out(copy)
+
+    def scenarios(self, mask=None) -> Dict[str, torch.Tensor]:
+        """The envs' episodes as set_scenarios takes them: clones of pose (N, 3), goal (N, 2), obst
+        (N, K, 4), obst_r (N, K) and episode (N,) — of the masked envs only (M rows, in env order)
+        with `mask`.  Fed back at t == 0 (straight after a reset or an injection) they reproduce the
+        env, later auto-resets included."""
+        self._check_open()
+        K = self.cfg.n_obst
+        d = {"pose": self.pose, "goal": self.goal, "obst": self.obst[:, :K], "obst_r": self.obst_r[:, :K],
+             "episode": self.episode}
+        if mask is None:
+            return {k: v.clone() for k, v in d.items()}
+        m = torch.as_tensor(mask).to(device=self.device, dtype=torch.bool).reshape(-1)
+        if m.numel() != self.num_envs:
+            raise ValueError("mask must have num_envs elements")
+        return {k: v[m].clone() for k, v in d.items()}
+
     def _actions(self, actions) -> torch.Tensor:
         a = torch.as_tensor(actions)
         if a.device != self.device or a.dtype != torch.int64:
@@ -1612,12 +1694,19 @@ class FFMPVec:
     # ------------------------------------------------------------ utilities
     def check_errors(self) -> None:
         """Raise if any step saw an action id outside 0..27 (bit 1; it was run as action 3) or a NaN
-        command (bit 2; it was run as (0, 0)).  Clears the bits."""
+        command (bit 2; it was run as (0, 0)), or set_scenarios a bad scenario (bit 4: a non-finite
+        word, a negative radius or |yaw| > 1024; the env was left as it was).  Clears the bits."""
         v = int(self.err.item())
         if v:
             self.err.zero_()
             if v == 1:  # the ids path alone: its message as it always was
                 raise ValueError(f"invalid action id(s) passed to FFMPVec.step (error bits {v:#x})")
+            if v & 4:
+                step = ([] if not v & 1 else ["invalid action id(s)"]) + ([] if not v & 2 else ["NaN command(s)"])
+                raise ValueError("bad scenario(s) passed to FFMPVec.set_scenarios (non-finite word, negative radius "
+                                 "or |yaw| > 1024: those envs were left unchanged)" +
+                                 (f" and {' and '.join(step)} passed to FFMPVec.step" if step else "") +
+                                 f" (error bits {v:#x})")
             what = ([] if not v & 1 else ["invalid action id(s)"]) + ([] if not v & 2 else ["NaN command(s)"])
             raise ValueError(f"{' and '.join(what) or 'errors'} passed to FFMPVec.step (error bits {v:#x}; "
                              "bit 2: NaN command)")

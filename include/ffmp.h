@@ -15,6 +15,9 @@
  *                          src/train.py:532-566 (start/goal, temporal stack
  *                          duplication, velocity := 0, d0 := dist) and the
  *                          commented-out FFMP.reset src/gym_ffmp/envs/ffmp.py:77-83
+ *   ffmp_set_scenario   -> the same is_first branch with the episode /episode_manager
+ *                          publishes on /start_goal_points (src/train.py:86,88,113-132)
+ *                          given by the caller instead of sampled
  *   ffmp_step, ffmp_step_fused -> one iteration of src/train.py:523-693 with Gazebo
  *                          (/cmd_vel integration), /bev_* rasterisers and
  *                          rewarder2 (src/gym_ffmp/envs/ffmp.py:179-188) in-GPU
@@ -121,7 +124,8 @@ typedef struct ffmp_state {
   int32_t* t;       /* (N)   steps since episode start               */
   int32_t* episode; /* (N)   episode counter (RNG key part)          */
   float* record;    /* (N, FFMP_REC_HDR + 12K) raster record */
-  uint32_t* err;    /* (1)   sticky error bits (value 1: bad action id, value 2: NaN command) */
+  uint32_t* err;    /* (1)   sticky error bits (value 1: bad action id, value 2: NaN command,
+                       value 4: bad scenario, ffmp_set_scenario) */
   /* Optional (NULL = not written): the post-step state of every env BEFORE auto-reset, i.e. what
    * the reference loop observes on the iteration that ends an episode (train.py:543-557) —
    * consumers that store transitions (a replay memory) need it for done envs. Written by
@@ -234,6 +238,31 @@ int ffmp_footprint(int32_t grid, double res, double robot_r,
 int ffmp_reset(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset,
                const uint8_t* mask, int32_t initial,
                ffmp_state_t* state, ffmp_obs_t* obs, void* stream);
+
+/* Injected episodes (an addition within ABI 9: no existing symbol, struct or value changes) — in the
+ * reference an episode's start and goal come from outside the env (/episode_manager publishes
+ * /start_goal_points, src/train.py:86,88,113-132) and the simulator holds the obstacles.
+ * ffmp_set_scenario is ffmp_reset with the sampled episode replaced by the caller's, for envs [0,n)
+ * where mask[e] != 0 (mask NULL = all).  DEVICE memory, float64, row e = env e:
+ *   pose (n, 3) x, y, yaw      goal (n, 2) world frame
+ *   obst (n, K, 4) x, y, vx, vy      obst_r (n, K)       (K = cfg->n_obst; both may be NULL with K == 0)
+ *   episode (n) int32: the env's new episode counter, or NULL: episode += 1 (as a masked ffmp_reset)
+ * Per selected env, in float64:
+ *   every word of pose / goal / obst / obst_r finite, every radius >= 0 and |yaw| <= 1024 (pi_to_pi
+ *   is the reference's loop, one turn per trip); otherwise the env is left untouched in every state,
+ *   observation and record word and error value 4 is ORed into *state->err
+ *   yaw := pi_to_pi(yaw); a disc with r == 0 is a parked disc (it never moves, nothing hits it), as
+ *   the sampler's; velocities are stored as given, also with cfg->moving == 0
+ *   t := 0; d0, state_g, state_v = 0, state_t = 0, lidar, grad and the raster record (word 10 = 1)
+ *   exactly as ffmp_reset computes them from its sampled episode
+ * Later auto-resets of the env return to the sampler, keyed (seed, episode + 1, env_offset + e).
+ * Call ffmp_raster (same mask) afterwards for state_m / potential, as after ffmp_reset.  The arrays
+ * are read with 8-byte loads (no alignment beyond float64's).  pose, goal (or obst, obst_r with
+ * K > 0) NULL, negative n or env_offset: FFMP_E_ARG; n == 0: nothing is launched. */
+int ffmp_set_scenario(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const uint8_t* mask,
+                      const double* pose, const double* goal, const double* obst, const double* obst_r,
+                      const int32_t* episode /* NULL ok */, ffmp_state_t* state, ffmp_obs_t* obs,
+                      void* stream);
 
 /* One env step for envs [0,n): action[e] in 0..27 (int64, train.py:343-345).
  * Integrates, moves obstacles, lidar, collision/goal/reward/done, truncation,
