@@ -123,6 +123,10 @@ _SIGS = {
     # injected episodes (an addition within ABI 9): ffmp_reset with the episode from (n, .) float64 arrays
     "ffmp_set_scenario": (C.c_int, [C.POINTER(CfgT), _I64, _I64, _P, _P, _P, _P, _P, _P, C.POINTER(StateT),
                                     C.POINTER(ObsT), _P]),
+    # the navigation field (an addition within ABI 9): cost-to-go / direction planes, target, geo_cost, cmd
+    "ffmp_nav_field": (C.c_int, [C.POINTER(CfgT), _I64, C.POINTER(ObsT), _P, _I64, _I32, _I32, _I32, C.c_double,
+                                 _P, _P, _P, _P, _P, _P]),
+    "ffmp_nav_field_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

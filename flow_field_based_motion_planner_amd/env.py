@@ -369,6 +369,21 @@ class FFMP(GymEnvBase):
             self._needs_reset = True
         return self._obs(), reward, done, info
 
+    def nav_field(self, **kw):
+        """The navigation field of the current observation (FFMPVec.nav_field, include/ffmp.h
+        ffmp_nav_field) of this one env, as NumPy values: target (2,) int32, geo_cost int,
+        geo_dist float (metres, inf when the goal is unreachable), and the cost / dir planes (G, G)
+        with cost=True / direction=True."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before nav_field()")
+        d = self._vec_env().nav_field(**kw)
+        out = {"target": d["target"][0].cpu().numpy(), "geo_cost": int(d["geo_cost"][0].item()),
+               "geo_dist": float(d["geo_dist"][0].item())}
+        for k in ("cost", "dir"):
+            if k in d:
+                out[k] = d[k][0].cpu().numpy()
+        return out
+
     def render(self, mode="human"):
         return None
 

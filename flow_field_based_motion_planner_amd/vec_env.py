@@ -1538,6 +1538,72 @@ class FFMPVec:
                                                   out.data_ptr(), self._stream()), "ffmp_policy_field")
         return out
 
+    # ------------------------------------------------ navigation field
+    NAV_DEFAULTS = dict(margin=2, soft_pen=40, lookahead=4, turn_sin=0.25)
+
+    def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
+                    cost=None, direction=None, target=None, geo_cost=None, cmd=None) -> None:
+        """One ffmp_nav_field launch over the current observation: the newest frame through the
+        window's strides and format, the ego goal from record words 8..9."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError(f"call reset() before {what}()")
+        knobs = (int(margin), int(soft_pen), int(lookahead))
+        _abi.check(self.lib.ffmp_nav_field_check(C.byref(self._cfg_c), self._fmt, *knobs), "ffmp_nav_field_check")
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_nav_field(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
+                                               self.record.data_ptr() + 8 * 4, self.record.stride(0), *knobs,
+                                               float(turn_sin), _ptr(cost), _ptr(direction), _ptr(target),
+                                               _ptr(geo_cost), _ptr(cmd), self._stream()), "ffmp_nav_field")
+
+    def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
+                  lookahead: int = 4) -> Dict[str, torch.Tensor]:
+        """The navigation field of the current observation, on the device (include/ffmp.h
+        ffmp_nav_field): the cost-to-go from the goal cell over the traversable cells of the newest
+        ego frame (hard = the footprint-dilated occupancy; a `margin`-cell zone around it costs
+        `soft_pen` extra per cell) and the direction per cell.  Returns
+          target   (N, 2) int32: the cell `lookahead` moves down the path, as offsets from the robot cell
+          geo_cost (N,) int32: the cost at the robot cell, -1 when the goal is unreachable
+          geo_dist (N,) float64 metres = geo_cost * res / 5, inf when unreachable — the chamfer 5-7
+                   approximation of the geodesic length (it overestimates a straight line by up to
+                   ~8 %), with the zone's penalties included
+          cost (N, G, G) uint16 (65535: hard or unreachable) with cost=True
+          dir  (N, G, G) uint8 (neighbour index 0..7, 8 at the goal, 255 unreachable) with direction=True
+        A static plan: obstacle velocities are not looked at.  Grids up to 256 x 256."""
+        n, G = self.num_envs, self.cfg.grid
+        out = {"target": torch.empty((n, 2), dtype=torch.int32, device=self.device),
+               "geo_cost": torch.empty(n, dtype=torch.int32, device=self.device)}
+        if cost:
+            out["cost"] = torch.empty((n, G, G), dtype=torch.uint16, device=self.device)
+        if direction:
+            out["dir"] = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
+        self._nav_launch("nav_field", margin, soft_pen, lookahead, self.NAV_DEFAULTS["turn_sin"],
+                         cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"])
+        gc = out["geo_cost"].to(torch.float64)
+        out["geo_dist"] = torch.where(gc < 0, torch.full_like(gc, float("inf")), gc * (self.cfg.res / 5.0))
+        return out
+
+    def policy_nav(self, out: Optional[torch.Tensor] = None, margin: int = 2, soft_pen: int = 40, lookahead: int = 4,
+                   turn_sin: float = 0.25) -> torch.Tensor:
+        """The next (v, w) commands (N, 2) float64 from the navigation field of the current
+        observation, on the device (include/ffmp.h ffmp_nav_field's follower): head for the cell
+        `lookahead` moves down the cheapest path, turning on the spot while it lies more than
+        asin(turn_sin) off the heading.  Complete on a static scene (it has no local minima, unlike
+        policy_field); stateless, so on an exactly symmetric scene it can dither between two equal
+        routes; obstacle velocities are not looked at.  (0, 0) when the goal is unreachable.  `out`:
+        write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before policy_nav()")
+        if out is None:
+            out = torch.empty((self.num_envs, 2), dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (self.num_envs, 2) or out.dtype != torch.float64 or not out.is_contiguous() \
+                or out.device != self.device or out.data_ptr() % 16:
+            raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
+                             f"({self.num_envs}, 2) on {self.device}")
+        self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out)
+        return out
+
     # ------------------------------------------------ HIP graph of whole steps
     def graph_period(self) -> int:
         """Steps after which the frame pair is back on the same ring slots (so one captured
@@ -1564,7 +1630,8 @@ class FFMPVec:
         step's observation (the first from the observation before the replay), and replay() takes
         no actions — the device-resident form of train.py:572-577's act-then-publish loop.  Plain
         two-launch (or one-launch) steps only: the policy reads the raster's frame.
-        Continuous (v, w) commands (SPEC a15b): policy="field" (policy_field; the static block is
+        Continuous (v, w) commands (SPEC a15b): policy="field" (policy_field) or policy="nav"
+        (policy_nav with its defaults; the static block is
         (steps, N, 2) float64 and replay() takes no actions), or commands=True for an open loop whose
         replay(cmds) takes a (steps, N, 2) block.  Command graphs run plain steps: pipelined=True or
         skewed=True raises ValueError (the skewed launch reads ids a step ahead), and their defaults
@@ -1832,14 +1899,14 @@ class StepGraph:
         if policy is not None:
             if pipelined or skewed:
                 raise ValueError("a closed-loop graph (policy) runs plain steps: the policy reads each raster's frame")
-            if policy not in ("reactive", "field") and not callable(policy):
-                raise ValueError("policy must be 'reactive', 'field' or a callable env -> (N,) int64 tensor")
+            if policy not in ("reactive", "field", "nav") and not callable(policy):
+                raise ValueError("policy must be 'reactive', 'field', 'nav' or a callable env -> (N,) int64 tensor")
             pipelined = skewed = False
         # (v, w) commands instead of ids: the field follower's closed loop, or an open loop (commands=True)
-        self.commands = bool(commands) or policy == "field"
+        self.commands = bool(commands) or policy in ("field", "nav")
         if self.commands:
             if callable(policy):
-                raise ValueError("commands=True takes policy='field' or no policy (a callable policy returns ids)")
+                raise ValueError("commands=True takes policy='field', 'nav' or no policy (a callable policy returns ids)")
             if policy == "reactive":
                 raise ValueError("policy='reactive' computes action ids, not commands")
             if pipelined or skewed:
@@ -1916,6 +1983,8 @@ class StepGraph:
             self.env.policy_reactive(out=self.actions[i])
         elif self.policy == "field":
             self.env.policy_field(out=self.actions[i])
+        elif self.policy == "nav":
+            self.env.policy_nav(out=self.actions[i])
         else:
             a = self.policy(self.env)
             if not (isinstance(a, torch.Tensor) and a.numel() == self.env.num_envs):

@@ -386,6 +386,61 @@ int ffmp_step_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const do
  * NULL, cmd misaligned: FFMP_E_ARG; n == 0: nothing is launched.  One lane per env. */
 int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, double* cmd, void* stream);
 
+/* A navigation field (an addition within ABI 9: no existing symbol, struct or value changes) — no
+ * reference counterpart (the reference plans with its Q-network, src/train.py:336-347; it has no
+ * path planner): the flow field of the pathfinding sense over the newest ego frame.  Per env, the
+ * cost-to-go from the goal cell over the traversable cells (an integration field), the direction
+ * per cell, and a follower that tracks the descent path from the robot cell.  All arithmetic is
+ * integer unless stated.  Inputs per env: the newest occupancy frame F (G x G through obs->state_m,
+ * its strides and format; row i = ego x = heading, column j = ego y; robot cell c = (G/2, G/2)) and
+ * the goal in the ego frame g = goal_ego[e * goal_stride + 0..1], float32 (FFMPVec: record words 8..9).
+ * Cell classes:
+ *   occ[i][j]  = F[i][j] > 0
+ *   hard[i][j] = any occ[i + di][j + dj] over the cfg->n_foot footprint offsets (offsets that fall
+ *                outside the grid are ignored)
+ *   zone       = hard dilated `margin` times by the 3 x 3 neighbourhood
+ *   goal cell  q = clamp(rint(((double)g + (double)half_f) / (double)res_f), 0, G - 1) per axis
+ *                (float64, rint half to even); a non-finite g makes the env unreachable (below)
+ *   then hard[c] = hard[q] = false;  soft = zone & ~hard (a cleared cell counts as soft)
+ *   pen(a) = soft[a] ? soft_pen : 0
+ * Neighbours, in this order k = 0..7: (1,0) (-1,0) (0,1) (0,-1) (1,1) (1,-1) (-1,1) (-1,-1), weight
+ * w_k = 5 for k < 4, else 7.  A diagonal move a -> a + (di, dj) is allowed only if neither
+ * a + (di, 0) nor a + (0, dj) is hard (no corner cutting).
+ * Cost-to-go d (uint16; 65535 = hard or unreachable): d[q] = 0; for every other non-hard cell
+ *   d[a] = pen(a) + min_k(d[a + k] + w_k) over in-grid, allowed neighbours with d < 65535,
+ * a candidate accepted only if it is <= 65534.  The fixed point is unique (prefixes of a shortest
+ * path are shorter), so the relaxation order does not show in the bits.
+ * Direction dir[a] (uint8): the k minimising d[a + k] + w_k under the same rules, the lowest k
+ * winning ties; 8 at q; 255 where d[a] == 65535.
+ * Robot outputs: geo_cost = d[c], or -1 if it is 65535.  From c follow dir for at most `lookahead`
+ * moves, stopping at q or where no neighbour qualifies: target = (ti - G/2, tj - G/2) of the cell
+ * reached.  An unreachable env (geo_cost -1) gets target (0, 0) and cmd (0, 0); an env with a
+ * non-finite g also gets cost 65535 and dir 255 in every cell.
+ * Follower, float64, in this order:
+ *   dx = target[0];  dy = target[1];  m2 = dx*dx + dy*dy;   m2 == 0: cmd = (0, 0)
+ *   else  m = sqrt(m2);  ux = dx / m;  uy = dy / m
+ *         w = uy / cfg->dt, then w < -0.6 ? -0.6 : (w > 0.6 ? 0.6 : w)    (ffmp_policy_field's compares)
+ *         if ux < 0:  w = uy >= 0 ? 0.6 : -0.6
+ *         v = 0.6 * (ux > 0 ? ux : 0.0)
+ *         if fabs(uy) > turn_sin:  v = 0.0      (turn on the spot: track the path, do not cut it)
+ * Defaults of the Python surface: margin 2, soft_pen 40, lookahead 4, turn_sin 0.25.
+ * cfg gives grid, the footprint, res_f, half_f and dt.  cost, dir (n, G, G), target (n, 2),
+ * geo_cost (n) and cmd (n, 2; what the *_cmd steps read) are DEVICE memory, each written only when
+ * non-NULL.  One workgroup per env holds the whole plane in LDS, so 8 <= G <= 256, G % 4 == 0.
+ * FFMP_E_ARG, with a message and before any HIP call, for: G outside that range; margin outside
+ * 0..8; soft_pen outside 0..16384; lookahead outside 1..64; turn_sin NaN or negative; obs,
+ * obs->state_m or goal_ego NULL; goal_stride < 2; cmd not 16-byte, cost not 8-byte or dir not 4-byte
+ * aligned; an unknown obs format; n < 0.  n == 0: nothing is launched.  Obstacle velocities are not
+ * looked at (a static plan over the newest frame), and the follower is stateless.
+ * ffmp_nav_field_check: the checks that need no pointer (shape, format, knobs, LDS budget), no launch. */
+int ffmp_nav_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs,
+                   const float* goal_ego, int64_t goal_stride /* floats between envs */,
+                   int32_t margin, int32_t soft_pen, int32_t lookahead, double turn_sin,
+                   uint16_t* cost /* (n,G,G) or NULL */, uint8_t* dir /* (n,G,G) or NULL */,
+                   int32_t* target /* (n,2) or NULL */, int32_t* geo_cost /* (n) or NULL */,
+                   double* cmd /* (n,2), 16-B aligned, or NULL */, void* stream);
+int ffmp_nav_field_check(const ffmp_cfg_t* cfg, int32_t format, int32_t margin, int32_t soft_pen, int32_t lookahead);
+
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
  *   local_map: float32 planes, env e at local_map + e*map_stride (G x G), or NULL
