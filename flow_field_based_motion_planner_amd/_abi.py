@@ -56,6 +56,17 @@ class ObsT(C.Structure):
                 ("format", C.c_int32), ("reserved", C.c_int32)]
 
 
+OBS_EXT_TAGS = 1  # FFMP_OBS_EXT_TAGS (ObsT.reserved): the struct is the head of an ObsTagsT
+TAG_CELLS = 64    # FFMP_TAG_CELLS: cells of a frame plane per granule tag
+
+
+class ObsTagsT(ObsT):
+    """ffmp_obs_tags_t: an ffmp_obs_t (its first member; the base class's fields, so that every
+    ObsT field keeps its name and C.byref() of it passes where an ObsT pointer is expected) followed
+    by the granule tags of the [older, newest] frame pair."""
+    _fields_ = [("tags_older", C.c_void_p), ("tags_newest", C.c_void_p), ("tags_env_stride", C.c_int64)]
+
+
 class OutT(C.Structure):
     _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("is_goal", C.c_void_p),
                 ("collide", C.c_void_p), ("truncated", C.c_void_p)]
@@ -220,6 +231,7 @@ def verify_layout(lib: Optional[C.CDLL] = None) -> None:
         4: CfgT.res.offset, 5: CfgT.res_f.offset, 6: CfgT.seed.offset, 7: CfgT.beam_cs.offset,
         8: C.sizeof(EpisodeT),
         9: ObsT.format.offset,
+        20: C.sizeof(ObsTagsT), 21: ObsTagsT.tags_older.offset,
     }
     for k, v in want.items():
         got = lib.ffmp_layout(k)

@@ -810,20 +810,75 @@ constexpr int FMT_F32 = 0, FMT_CT4 = 1, FMT_CT16 = 2, FMT_CT8 = 3;
 #define FFMP_CT8_MIN_WAVES 6
 #endif
 
+// Granule tags (include/ffmp.h ffmp_obs_tags_t, float32 frames): one byte per 64 consecutive cells of
+// a frame plane, per (physical frame slot, env).  tag == 0 promises that the granule's 64 cells in that
+// slot are 0.0f; 1 = unknown or non-zero.  A 16-lane group of a wave task owns exactly one granule (4
+// cells per lane; row runs, TILE2 and TILE4), so per frame it writes: nz = any of its 16 occupancy
+// words non-zero (one ballot), it stores the frame only if nz || old tag, and writes the tag := nz.
+// The values stored are the ones the dense raster stores, so every frame stays bit-identical; a
+// frame of an obstacle-sparse world skips ~94 % of its 16-B stores.
+// The old tags are read once per block into LDS, beside the record and before the block's first
+// store: a tag loaded inside the task loop would sit on the VM counter behind the previous task's
+// stores (counted in order), and the wave would drain them before every store decision.  Blocks own
+// whole multiples of 1024 cells, so no two blocks share a tag byte.
+// Shapes whose 16-lane groups are not granules (TILE8 / TILE16 row segments of 32 / 16 cells) and
+// blocks of more than kTagLdsCap granules store everything and write tag 1 (skip == false).
+constexpr int kTagLdsCap = 1024;  // granules of one slot a block stages (a whole 256 x 256 plane)
+struct TagArgs {
+  uint8_t* older;      // tags of the slot of state_m[:, 0], env 0
+  uint8_t* newest;     // tags of the slot of state_m[:, 1], env 0
+  int64_t env_stride;  // bytes from env e's tags to env e + 1's
+};
+struct TagLds {
+  uint8_t older[kTagLdsCap], newest[kTagLdsCap];
+};
+struct TagCtx {
+  uint8_t* t0;        // this env's tags, older slot
+  uint8_t* t1;        // ... newest slot
+  const uint8_t* s0;  // the block's old tags in LDS (from granule g0 on)
+  const uint8_t* s1;
+  int g0;
+  bool skip;          // block-uniform: the groups of this launch shape may skip stores
+};
+template <class T>
+FFMP_DEV const T& first_arg(const T& a) { return a; }
+
+// Stage the old tags of cells [qbeg, qend) of env e (threads t = 0 .. nt-1 of the block; t < 0: none);
+// the caller's next block barrier publishes them.
+FFMP_DEV TagCtx stage_tags(const TagArgs& ta, int64_t e, int qbeg, int qend, int32_t tile_log2r, TagLds& L, int t,
+                           int nt) {
+  TagCtx c;
+  c.t0 = ta.older + e * ta.env_stride;
+  c.t1 = ta.newest + e * ta.env_stride;
+  c.s0 = L.older;
+  c.s1 = L.newest;
+  c.g0 = qbeg >> 6;
+  const int ng = (qend - qbeg + 63) >> 6;
+  c.skip = tile_log2r < 3 && ng <= kTagLdsCap;
+  if (c.skip && t >= 0) {
+    for (int i = t; i < ng; i += nt) {
+      L.older[i] = c.t0[c.g0 + i];
+      L.newest[i] = c.t1[c.g0 + i];
+    }
+  }
+  return c;
+}
+
 // The raster of cells [tile * cells_per_block, ...) of env e by the whole 256-thread block
 // (block-uniform arguments; contains a block barrier).  Compact formats: state_m holds uint8
 // frames and pot binary16 planes (the pointers are reinterpreted; strides in elements).
 // PRELOADED: the record is already in the block's LDS (s_hdr, s_cur, s_prev, s_vel; written by the
 // one-launch step's env_group before a block barrier), so the raster does not read it back from HBM.
-template <bool NT, bool FLOW, int FMT, bool PRELOADED = false>
+template <bool NT, bool FLOW, int FMT, bool PRELOADED = false, bool TAGS = false>
 FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, int64_t e, int tile, int32_t cells_per_block,
                                                         const float* __restrict__ record,
                                                         float* __restrict__ state_m, int64_t sm_stride,
                                                         int64_t sm_frame, int32_t newest_only,
                                                         float* __restrict__ pot, float* __restrict__ flow,
                                                         int32_t tile_log2r, float4* s_cur, float4* s_prev,
-                                                        float2* s_vel, float* s_hdr) {
+                                                        float2* s_vel, float* s_hdr, const TagCtx& tagc = TagCtx{}) {
   constexpr bool CT = FMT != FMT_F32;
+  static_assert(!TAGS || FMT == FMT_F32, "granule tags: float32 frames only");
   constexpr int CPL = FMT == FMT_CT16 ? 16 : FMT == FMT_CT8 ? 8 : 4;  // cells per lane in a wave task
   constexpr int WC = 64 * CPL;                   // cells per wave task
   const int K = cfg.n_obst;
@@ -884,6 +939,21 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
 
   const int qbeg = tile * cells_per_block;
   const int qend = min(qbeg + cells_per_block, G2);
+
+  // TAGS: does this lane's 16-lane group (one granule, at plane offset q) store its frame words
+  // (nzlane: this lane's are not all zero)?  Writes the granule's tag.  Called by every lane that
+  // has cells, under block-uniform conditions only.
+  [[maybe_unused]] auto tag_gate = [&](bool nzlane, uint8_t* t, const uint8_t* s, int q) -> bool {
+    const int g = q >> 6;
+    if (!tagc.skip) {
+      if ((q & 15) == 0) t[g] = 1;
+      return true;
+    }
+    const bool nz = ((__ballot(nzlane) >> (lane & 48)) & 0xFFFFull) != 0ull;
+    const bool old = s[g - tagc.g0] != 0;
+    if ((lane & 15) == 0) t[g] = nz ? 1 : 0;
+    return nz || old;
+  };
 
   // One wave task: the cells of ego rows [i0, i1] x columns [j0, j1] (the cull box), this
   // lane's CPL cells (i, j..j+CPL-1) at plane offset q, `valid` = the lane has cells.
@@ -979,8 +1049,14 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
       }
       return;
     }
-    if (write_old) store4<NT>(m0 + q, occp[0] * 255.0f, occp[1] * 255.0f, occp[2] * 255.0f, occp[3] * 255.0f);
-    store4<NT>(m1 + q, occc[0] * 255.0f, occc[1] * 255.0f, occc[2] * 255.0f, occc[3] * 255.0f);
+    [[maybe_unused]] bool st_p = true, st_c = true;
+    if constexpr (TAGS) {
+      if (write_old) st_p = tag_gate((occp[0] + occp[1]) + (occp[2] + occp[3]) != 0.0f, tagc.t0, tagc.s0, q);
+      st_c = tag_gate((occc[0] + occc[1]) + (occc[2] + occc[3]) != 0.0f, tagc.t1, tagc.s1, q);
+    }
+    if (write_old && (!TAGS || st_p))
+      store4<NT>(m0 + q, occp[0] * 255.0f, occp[1] * 255.0f, occp[2] * 255.0f, occp[3] * 255.0f);
+    if (!TAGS || st_c) store4<NT>(m1 + q, occc[0] * 255.0f, occc[1] * 255.0f, occc[2] * 255.0f, occc[3] * 255.0f);
     if (pp) store4<NT>(pp + q, U[0], U[1], U[2], U[3]);
     if (FLOW) {
       store4<NT>(f0 + q, fx[0], fx[1], fx[2], fx[3]);
@@ -1165,11 +1241,17 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
             }
           } else {
             // byte 0xFF -> 255.0f, 0 -> 0.0f: the reference layout's occ * 255 values
-            if (write_old)
+            [[maybe_unused]] bool st_p = true, st_c = true;
+            if constexpr (TAGS) {
+              if (write_old) st_p = tag_gate(wp[0] != 0u, tagc.t0, tagc.s0, q);
+              st_c = tag_gate(wc[0] != 0u, tagc.t1, tagc.s1, q);
+            }
+            if (write_old && (!TAGS || st_p))
               store4<NT>(m0 + q, (float)(wp[0] & 0xFFu), (float)((wp[0] >> 8) & 0xFFu), (float)((wp[0] >> 16) & 0xFFu),
                          (float)(wp[0] >> 24));
-            store4<NT>(m1 + q, (float)(wc[0] & 0xFFu), (float)((wc[0] >> 8) & 0xFFu), (float)((wc[0] >> 16) & 0xFFu),
-                       (float)(wc[0] >> 24));
+            if (!TAGS || st_c)
+              store4<NT>(m1 + q, (float)(wc[0] & 0xFFu), (float)((wc[0] >> 8) & 0xFFu), (float)((wc[0] >> 16) & 0xFFu),
+                         (float)(wc[0] >> 24));
             if (pp) store4<NT>(pp + q, U2[0].x, U2[0].y, U2[NP - 1].x, U2[NP - 1].y);
             if (FLOW) {
               store4<NT>(f0 + q, fx[0], fx[1 % CPL], fx[2 % CPL], fx[3 % CPL]);
@@ -1204,7 +1286,9 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
   }
 }
 
-template <bool NT, bool XCD, bool FLOW, int FMT>
+// TG: nothing, or one TagArgs (granule tags; an instantiation of its own, so that the launches
+// without tags keep their code)
+template <bool NT, bool XCD, bool FLOW, int FMT, class... TG>
 __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES : 1)) void raster_kernel(ffmp_cfg_t cfg, int64_t n, int32_t bpe,
                                                      int32_t cells_per_block,
                                                      const float* __restrict__ record,
@@ -1212,7 +1296,8 @@ __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES 
                                                      float* __restrict__ state_m, int64_t sm_stride,
                                                      int64_t sm_frame, int32_t newest_only,
                                                      float* __restrict__ pot,
-                                                     float* __restrict__ flow, int32_t tile_log2r) {
+                                                     float* __restrict__ flow, int32_t tile_log2r, TG... tg) {
+  constexpr bool TAGS = sizeof...(TG) != 0;
   __shared__ float4 s_cur[FFMP_MAX_OBST], s_prev[FFMP_MAX_OBST];
   __shared__ float2 s_vel[FLOW ? FFMP_MAX_OBST : 1];
   __shared__ float s_hdr[FFMP_REC_HDR];
@@ -1221,8 +1306,15 @@ __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES 
   const int tile = (int)(lb - e * bpe);
   if (e >= n) return;
   if (mask && !mask[e]) return;
-  raster_env<NT, FLOW, FMT>(cfg, e, tile, cells_per_block, record, state_m, sm_stride, sm_frame, newest_only, pot, flow,
-                       tile_log2r, s_cur, s_prev, s_vel, s_hdr);
+  [[maybe_unused]] TagCtx tc{};
+  if constexpr (TAGS) {  // published by raster_env's barrier behind the record
+    __shared__ TagLds s_tags;
+    const int qbeg = tile * cells_per_block;
+    tc = stage_tags(first_arg(tg...), e, qbeg, min(qbeg + cells_per_block, cfg.grid * cfg.grid), tile_log2r, s_tags,
+                    (int)threadIdx.x, 256);
+  }
+  raster_env<NT, FLOW, FMT, false, TAGS>(cfg, e, tile, cells_per_block, record, state_m, sm_stride, sm_frame, newest_only,
+                                         pot, flow, tile_log2r, s_cur, s_prev, s_vel, s_hdr, tc);
 #ifdef FFMP_TRACE
   __syncthreads();
   FFMP_RAS_STAMP(2);
@@ -1241,12 +1333,13 @@ __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES 
 template <bool FLOW, int FMT>
 constexpr int kFusedMinWaves = (FMT == FMT_CT4 && !FLOW) ? 7 : (FMT == FMT_CT8 && !FLOW) ? FFMP_CT8_MIN_WAVES : 1;
 
-template <bool NT, bool XCD, bool FLOW, int FMT, bool CMD = false>
+template <bool NT, bool XCD, bool FLOW, int FMT, bool CMD = false, class... TG>
 __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
                                                           const act_t<CMD>* __restrict__ action, ffmp_state_t st,
                                                           ffmp_obs_t ob, ffmp_out_t out, int64_t sm_stride,
                                                           int64_t sm_frame, int32_t newest_only,
-                                                          int32_t tile_log2r) {
+                                                          int32_t tile_log2r, TG... tg) {
+  constexpr bool TAGS = sizeof...(TG) != 0;
   __shared__ double s_ox[FFMP_MAX_OBST], s_oy[FFMP_MAX_OBST], s_or[FFMP_MAX_OBST], s_orr[FFMP_MAX_OBST];
   __shared__ float4 s_ecur[FFMP_MAX_OBST], s_eprev[FFMP_MAX_OBST];
   __shared__ float2 s_foot[FFMP_MAX_FOOT + 1];  // + the cells' extent
@@ -1255,6 +1348,11 @@ __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_
   const int64_t e = logical_block<XCD>();
   if (e >= n) return;
   FFMP_RAS_STAMP(0);
+  [[maybe_unused]] TagCtx tc{};
+  if constexpr (TAGS) {  // waves 1..3 stage the plane's old tags while wave 0 steps the env
+    __shared__ TagLds s_tags;
+    tc = stage_tags(first_arg(tg...), e, 0, cfg.grid * cfg.grid, tile_log2r, s_tags, (int)threadIdx.x - 64, 192);
+  }
   if (threadIdx.x < 64) {
     stage_footprint(cfg, s_foot);
     // (one beam at a time where the block is held to more than 4 waves per SIMD: the chunked
@@ -1267,8 +1365,8 @@ __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_
   // stored to st.record — so the raster starts without a round trip to HBM for them.
   __syncthreads();
   FFMP_RAS_STAMP(3);
-  raster_env<NT, FLOW, FMT, true>(cfg, e, 0, cfg.grid * cfg.grid, st.record, ob.state_m, sm_stride, sm_frame, newest_only,
-                       ob.potential, ob.flow, tile_log2r, s_ecur, s_eprev, s_vel, s_hdr);
+  raster_env<NT, FLOW, FMT, true, TAGS>(cfg, e, 0, cfg.grid * cfg.grid, st.record, ob.state_m, sm_stride, sm_frame,
+                                        newest_only, ob.potential, ob.flow, tile_log2r, s_ecur, s_eprev, s_vel, s_hdr, tc);
 #ifdef FFMP_TRACE
   __syncthreads();
   FFMP_RAS_STAMP(2);
@@ -1297,13 +1395,14 @@ struct SkewRasterLds {
   float hdr[FFMP_REC_HDR];
 };
 
-template <bool NT, bool XCD, int LPE>
+template <bool NT, bool XCD, int LPE, class... TG>
 __global__ __launch_bounds__(256) void skew_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
                                                    const int64_t* __restrict__ action, ffmp_state_t st, ffmp_obs_t ob,
                                                    ffmp_out_t out, int32_t env_chunks, int32_t chunk_s, int32_t bpe,
                                                    int32_t cells_per_block, const float* __restrict__ record_r,
                                                    int64_t sm_stride, int64_t sm_frame, int32_t newest_only,
-                                                   int32_t tile_log2r) {
+                                                   int32_t tile_log2r, TG... tg) {
+  constexpr bool TAGS = sizeof...(TG) != 0;
   constexpr int W = 4, EPW = 64 / LPE;
   constexpr size_t kEnvB = sizeof(SkewEnvLds<LPE>), kRasB = sizeof(SkewRasterLds);
   __shared__ __attribute__((aligned(16))) char smem[kEnvB > kRasB ? kEnvB : kRasB];
@@ -1346,8 +1445,15 @@ __global__ __launch_bounds__(256) void skew_kernel(ffmp_cfg_t cfg, int64_t n, in
   const int64_t e = lb / bpe;
   const int tile = (int)(lb - e * bpe);
   if (e >= n) return;
-  raster_env<NT, false, FMT_F32>(cfg, e, tile, cells_per_block, record_r, ob.state_m, sm_stride, sm_frame, newest_only,
-                                 ob.potential, nullptr, tile_log2r, R.cur, R.prev, R.vel, R.hdr);
+  [[maybe_unused]] TagCtx tc{};
+  if constexpr (TAGS) {
+    __shared__ TagLds s_tags;
+    const int qbeg = tile * cells_per_block;
+    tc = stage_tags(first_arg(tg...), e, qbeg, min(qbeg + cells_per_block, cfg.grid * cfg.grid), tile_log2r, s_tags,
+                    (int)threadIdx.x, 256);
+  }
+  raster_env<NT, false, FMT_F32, false, TAGS>(cfg, e, tile, cells_per_block, record_r, ob.state_m, sm_stride, sm_frame,
+                                              newest_only, ob.potential, nullptr, tile_log2r, R.cur, R.prev, R.vel, R.hdr, tc);
 }
 
 // ============================================================================
@@ -1750,6 +1856,23 @@ int raster_format(bool compact, int grid, int32_t flags) {
   return grid % 16 == 0 ? FMT_CT16 : FMT_CT4;
 }
 
+// The granule tags behind an ffmp_obs_t with FFMP_OBS_EXT_TAGS (include/ffmp.h ffmp_obs_tags_t), checked;
+// *on = false without the flag.
+int obs_tags(const ffmp_cfg_t* cfg, const ffmp_obs_t* o, TagArgs* t, bool* on) {
+  *on = (o->reserved & FFMP_OBS_EXT_TAGS) != 0;
+  if (!*on) return FFMP_OK;
+  const ffmp_obs_tags_t* x = reinterpret_cast<const ffmp_obs_tags_t*>(o);
+  if (o->format != FFMP_OBS_F32)
+    return fail(FFMP_E_ARG, "FFMP_OBS_EXT_TAGS: granule tags need format FFMP_OBS_F32, got %d", o->format);
+  if (!x->tags_older || !x->tags_newest) return fail(FFMP_E_ARG, "FFMP_OBS_EXT_TAGS: tags_older / tags_newest is NULL");
+  const int64_t T = ((int64_t)cfg->grid * cfg->grid + FFMP_TAG_CELLS - 1) / FFMP_TAG_CELLS;
+  if (x->tags_env_stride < T)
+    return fail(FFMP_E_ARG, "FFMP_OBS_EXT_TAGS: tags_env_stride %lld < %lld tags per frame",
+                (long long)x->tags_env_stride, (long long)T);
+  *t = TagArgs{x->tags_older, x->tags_newest, x->tags_env_stride};
+  return FFMP_OK;
+}
+
 // The scripted reactive controller of ffmp_policy_reactive: one thread per env reads the env's
 // relative goal and a short ray of cells ahead of the robot on its newest frame (row index = ego
 // x = heading, ffmp_device.h cell_coord), and picks the action id 7 * vi + wi (config.py:25-58).
@@ -1910,6 +2033,8 @@ int64_t ffmp_layout(int32_t which) {
     case 7: return (int64_t)offsetof(ffmp_cfg_t, beam_cs);
     case 8: return (int64_t)sizeof(ffmp_episode_t);
     case 9: return (int64_t)offsetof(ffmp_obs_t, format);
+    case 20: return (int64_t)sizeof(ffmp_obs_tags_t);
+    case 21: return (int64_t)offsetof(ffmp_obs_tags_t, tags_older);
     default: return -1;
   }
 }
@@ -2031,6 +2156,9 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
     return fail(FFMP_E_ARG, "cells_per_block must be 0 or a multiple of 1024, got %d", cells_per_block);
   if ((flags & FFMP_RASTER_NT) && (flags & FFMP_RASTER_PLAIN)) return fail(FFMP_E_ARG, "NT and PLAIN both set");
   if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
+  TagArgs tags{};
+  bool tagged = false;
+  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
   if (n == 0) return FFMP_OK;
   const int G2 = cfg->grid * cfg->grid;
   const int cpb_max = cells_per_block ? cells_per_block : 4096;
@@ -2074,12 +2202,31 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
     float* pot = obs->potential ? (float*)((char*)obs->potential + e0 * (int64_t)G2 * (ct ? 2 : 4)) : nullptr;
     float* flw = obs->flow ? (float*)((char*)obs->flow + e0 * 2 * (int64_t)G2 * (ct ? 2 : 4)) : nullptr;
     dispatch_variant(fmt, nt, xcd, fl, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
+      if constexpr (decltype(FMT_)::value == FMT_F32) {
+        if (tagged) {
+          const TagArgs tg{tags.older + e0 * tags.env_stride, tags.newest + e0 * tags.env_stride, tags.env_stride};
+          hipLaunchKernelGGL((raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, TagArgs>),
+                             grid, block, tuning().lds_pad, s, *cfg, m, bpe, cpb, rec, msk, sm, sm_stride, sm_frame, newest,
+                             pot, flw, tile_log2r, tg);
+          return;
+        }
+      }
       hipLaunchKernelGGL((raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value>), grid, block, tuning().lds_pad, s, *cfg, m,
                          bpe, cpb, rec, msk, sm, sm_stride, sm_frame, newest, pot, flw, tile_log2r);
     });
     if (int rc2 = check_launch("ffmp_raster")) return rc2;
   }
   return FFMP_OK;
+}
+
+// ffmp_step / ffmp_step_cmd: a bad tag extension is refused before the env kernel is launched (the
+// other argument errors are the two launches' own, in their order)
+static int check_tags_first(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs) {
+  if (!cfg || !obs || !(obs->reserved & FFMP_OBS_EXT_TAGS)) return FFMP_OK;
+  if (int rc = check_cfg(cfg)) return rc;
+  TagArgs t{};
+  bool on = false;
+  return obs_tags(cfg, obs, &t, &on);
 }
 
 int ffmp_raster(const ffmp_cfg_t* cfg, int64_t n, const float* record, const uint8_t* mask, ffmp_obs_t* obs,
@@ -2092,14 +2239,18 @@ int ffmp_raster(const ffmp_cfg_t* cfg, int64_t n, const float* record, const uin
 
 int ffmp_step(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action,
               ffmp_state_t* state, ffmp_obs_t* obs, ffmp_out_t* out, void* stream) {
-  int rc = ffmp_step_state(cfg, n, env_offset, action, state, obs, out, stream);
+  int rc = check_tags_first(cfg, obs);
+  if (rc) return rc;
+  rc = ffmp_step_state(cfg, n, env_offset, action, state, obs, out, stream);
   if (rc) return rc;
   return ffmp_raster(cfg, n, state->record, nullptr, obs, stream);
 }
 
 int ffmp_step_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const double* cmd, ffmp_state_t* state,
                   ffmp_obs_t* obs, ffmp_out_t* out, void* stream) {
-  int rc = ffmp_step_state_cmd(cfg, n, env_offset, cmd, state, obs, out, stream);
+  int rc = check_tags_first(cfg, obs);
+  if (rc) return rc;
+  rc = ffmp_step_state_cmd(cfg, n, env_offset, cmd, state, obs, out, stream);
   if (rc) return rc;
   return ffmp_raster(cfg, n, state->record, nullptr, obs, stream);
 }
@@ -2125,6 +2276,9 @@ static int step_fused(bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   const bool fl = cfg->flow != 0;
   if (fl && !obs->flow) return fail(FFMP_E_ARG, "cfg.flow is set but obs.flow is NULL");
   if (int rc2 = check_format(obs, fl)) return rc2;
+  TagArgs tags{};
+  bool tagged = false;
+  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
   const bool ct = obs->format == FFMP_OBS_U8F16;
   if (n == 0) return FFMP_OK;
   if (n > 0x7fffffffLL / 256) return fail(FFMP_E_ARG, "n too large for one launch: %lld", (long long)n);  // one block per env
@@ -2147,6 +2301,19 @@ static int step_fused(bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   hipStream_t s = (hipStream_t)stream;
   ffmp_out_t o = *out;
   dispatch_variant(fmt, nt, xcd, fl, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
+    if constexpr (decltype(FMT_)::value == FMT_F32) {
+      if (tagged) {
+        if (cmd)
+          hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, true, TagArgs>),
+                             grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const double2*>(action), *state,
+                             *obs, o, sm_stride, sm_frame, newest, tile_log2r, tags);
+        else
+          hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, false, TagArgs>),
+                             grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const int64_t*>(action), *state,
+                             *obs, o, sm_stride, sm_frame, newest, tile_log2r, tags);
+        return;
+      }
+    }
     if (cmd)
       hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value, true>), grid, block, tuning().lds_pad, s, *cfg, n,
                          env_offset, static_cast<const double2*>(action), *state, *obs, o, sm_stride, sm_frame, newest, tile_log2r);
@@ -2201,6 +2368,9 @@ static int step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, con
   if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
   // the instances there are: float32 frames, no flow planes, one disc per lane on 8..64 lanes
   if (obs->format != FFMP_OBS_F32 || cfg->flow) return fail(FFMP_E_ARG, "ffmp_step_skewed: float32 frames without flow planes only");
+  TagArgs tags{};
+  bool tagged = false;
+  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
   const int lpe = cfg->n_obst <= 8 ? 8 : cfg->n_obst <= 16 ? 16 : cfg->n_obst <= 32 ? 32 : 64;
   if (n == 0) return FFMP_OK;
   const int G2 = cfg->grid * cfg->grid;
@@ -2243,8 +2413,14 @@ static int step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, con
                  ? (size_t)a.sharedSizeBytes
                  : (size_t)0;
     }();
-    if (static_lds + keys > device_lds_limit()) return false;
+    if (static_lds + (tagged ? sizeof(TagLds) : 0) + keys > device_lds_limit()) return false;
     if (dry_run) return true;
+    if (tagged) {
+      hipLaunchKernelGGL((skew_kernel<kNT, kXCD, kL, TagArgs>), grid, block, keys, s, *cfg, n, env_offset, action_next,
+                         *state_next, *obs, o, (int32_t)env_chunks, (int32_t)chunk_s, bpe, cpb, record_raster, sm_stride,
+                         sm_frame, newest, tile_log2r, tags);
+      return true;
+    }
     hipLaunchKernelGGL((skew_kernel<kNT, kXCD, kL>), grid, block, keys, s, *cfg, n, env_offset, action_next, *state_next,
                        *obs, o, (int32_t)env_chunks, (int32_t)chunk_s, bpe, cpb, record_raster, sm_stride, sm_frame,
                        newest, tile_log2r);

@@ -132,6 +132,14 @@ class FFMPVec:
         info_format: "dict" (default): step()'s info is one dict of (N,) device tensors (is_goal,
             collision, truncated, step, episode).  "list": gym 0.17/0.18 VectorEnv's form, a tuple
             of N per-env dicts of Python scalars (one device -> host copy per step).
+        sparse_frames: keep one tag per 64-cell granule of every (ring slot, env) — `frame_tags`
+            (slots, N, ceil(G*G/64)) uint8 in the arena, tag 0 = the granule holds zeros — and let
+            the raster skip the frame stores that would write zeros over zeros (include/ffmp.h
+            ffmp_obs_tags_t): about half the bytes of a C3 step, every value unchanged.  None
+            (default): on for obs_format="f32" with pipeline == 1 (pipelined slices and the
+            compact format store densely; asking for it there raises ValueError).  The frame
+            ring is then read-only for consumers: a caller that writes into it calls
+            invalidate_frame_tags() before the next step (`frames` does so each time it is taken).
     """
 
     def __init__(self, num_envs: int, config: Union[FFMPConfig, str] = "C3",
@@ -140,7 +148,8 @@ class FFMPVec:
                  autotune: bool = True, pipeline: Optional[int] = None, keep_terminal: bool = False,
                  frame_window: Optional[int] = None, seamless: Optional[bool] = None,
                  fused: Optional[bool] = None, tuning: Optional[dict] = None, obs_format: str = "f32",
-                 hbm_budget: Optional[int] = None, bev_series: int = 0, info_format: str = "dict"):
+                 hbm_budget: Optional[int] = None, bev_series: int = 0, info_format: str = "dict",
+                 sparse_frames: Optional[bool] = None):
         if isinstance(config, str):
             config = preset(config)
         if seed is not None:
@@ -166,6 +175,13 @@ class FFMPVec:
         self._fmt, self._frame_dtype, self._pot_dtype = self.OBS_FORMATS[obs_format]
         self._fes = torch.empty((), dtype=self._frame_dtype).element_size()  # bytes per frame cell
         self._pes = torch.empty((), dtype=self._pot_dtype).element_size()    # bytes per potential cell
+        # granule tags (include/ffmp.h ffmp_obs_tags_t): the raster skips the frame stores that would
+        # write zeros over zeros.  float32 frames, the serial step (pipelined slices launch their
+        # rasters per env slice through plain ffmp_obs_t structs: they run dense)
+        slices = 1 if pipeline is None else max(1, min(int(pipeline), self.num_envs))
+        if sparse_frames and (obs_format != "f32" or slices > 1):
+            raise ValueError("sparse_frames=True needs obs_format='f32' and pipeline=1")
+        self.sparse_frames = (obs_format == "f32" and slices == 1) if sparse_frames is None else bool(sparse_frames)
         self.env_offset = int(env_offset)
         self.with_potential = bool(potential)
         self.hbm_budget = None if hbm_budget is None else int(hbm_budget)
@@ -319,8 +335,9 @@ class FFMPVec:
         plane = N * G2 * self._fes
         budget = self.hbm_budget
         if budget is not None:  # what fits: the arena (other planes, state) + W ring slots
-            rest = budget - self._arena_estimate(with_frames=False)
-            w_fit = rest // self._ring_stride(plane)
+            rest = budget - self._arena_estimate(with_frames=False)  # (holds the tags of 2 slots)
+            tag_slot = N * self._tags_per_frame() if self.sparse_frames else 0
+            w_fit = (rest + 2 * tag_slot) // (self._ring_stride(plane) + tag_slot)
             if rest < 2 * plane:
                 raise ValueError(f"hbm_budget {budget} B cannot hold {N} envs' planes "
                                  f"({self._arena_estimate(with_frames=False) + 2 * plane} B at W = 2)")
@@ -352,6 +369,8 @@ class FFMPVec:
              self._frame_dtype),
             ("potential", (N, G, G), self._pot_dtype),
             ("flow", (N, 2, G, G), self._pot_dtype),  # float16 in the compact layout, like the potential
+            # sparse_frames: one tag per 64-cell granule of every (physical frame slot, env)
+            ("frame_tags", (max(getattr(self, "frame_window", 2), 2), N, self._tags_per_frame()), torch.uint8),
             # state
             ("pose", (N, 3), f64), ("goal", (N, 2), f64), ("d0", (N,), f64),
             ("obst", (N, max(K, 1), 4), f64), ("obst_r", (N, max(K, 1)), f64),
@@ -371,6 +390,8 @@ class FFMPVec:
             specs = [sp for sp in specs if sp[0] != "potential"]
         if not cfg.flow:
             specs = [sp for sp in specs if sp[0] != "flow"]
+        if not getattr(self, "sparse_frames", False):
+            specs = [sp for sp in specs if sp[0] != "frame_tags"]
         if L == 0:
             specs = [sp for sp in specs if sp[0] != "lidar"]
         if not self.keep_terminal:
@@ -380,6 +401,51 @@ class FFMPVec:
         if not with_frames:
             specs = [sp for sp in specs if sp[0] != "frames"]
         return specs
+
+    def _tags_per_frame(self) -> int:
+        """Granule tags per frame plane: ceil(G * G / 64) (include/ffmp.h FFMP_TAG_CELLS)."""
+        return -(-self.cfg.grid * self.cfg.grid // _abi.TAG_CELLS)
+
+    frame_tags = None  # (slots, N, ceil(G*G/64)) uint8, sparse_frames only
+    _frames = None
+
+    @property
+    def frames(self) -> Optional[torch.Tensor]:
+        """The frame ring itself: (W, N, G, G) slot-major ((W + 1, ...) for the seamless ring, slot W
+        aliasing slot 0), or (N, 2, G, G) with W = 2.  This is the handle through which a caller can
+        write frame memory, so with sparse_frames taking it counts as a write: every tag is set to
+        unknown (invalidate_frame_tags()), and the next raster into each slot stores all of its
+        cells.  Take it to inspect or to overwrite the ring, not in the step loop; `state_m`,
+        temporal_maps() and bev_maps() read the ring without that cost."""
+        self.invalidate_frame_tags()
+        return self._frames
+
+    @frames.setter
+    def frames(self, t: Optional[torch.Tensor]) -> None:
+        self._frames = t
+
+    def invalidate_frame_tags(self, slots=None) -> None:
+        """Mark the frames of the physical ring slots `slots` (an index, a list or a slice of
+        frame_tags' first dimension; None: all) as unknown, so that the next raster into them stores
+        every cell.  The frame ring is read-only for consumers: whoever writes frame memory behind
+        the raster's back (torch ops on `frames` / `state_m`, a new or re-mapped ring) calls this
+        before the next step, or a granule tagged all-zero keeps whatever was written into it.
+        A no-op without sparse_frames."""
+        if self.frame_tags is None:
+            return
+        if slots is None:
+            self.frame_tags.fill_(1)
+        else:
+            self.frame_tags[slots] = 1
+
+    def frame_tag_density(self) -> float:
+        """Mean tag of the newest frame's slot: the share of that frame's granules that hold a
+        non-zero cell (or are unknown) — a diagnostic, computed with torch outside any timed
+        region (it synchronizes); NaN without tags.  C3: about 0.04."""
+        if self.frame_tags is None:
+            return float("nan")
+        slot = (self._wpos + 1) % self.frame_tags.shape[0]
+        return float(self.frame_tags[slot].ne(0).float().mean().item())
 
     NO_VMM = "has no virtual memory management"  # ffmp_ring_create's message (ffmp_ring.hip ring_geom)
 
@@ -407,7 +473,7 @@ class FFMPVec:
                 torch.cuda.empty_cache()
                 self._ring = _abi.SeamlessRing(self.device.index, (N, G, G), self.frame_window, bits=8 * self._fes,
                                                partner=partner)
-            self.frames = self._ring.tensor
+            self._frames = self._ring.tensor
             self.ring_meta = self._ring.info()
             if partner is not None:
                 self._note_partner()
@@ -443,13 +509,14 @@ class FFMPVec:
         keep = keep_ring and self.ring == "seamless"
         want_ring = keep or self._seamless_req is not False
         if not keep:
-            self.frames = None
+            self._frames = None
             self._ring = None
             self.ring_meta = None
         specs = self._buffer_specs(with_frames=not want_ring)
         self.potential = None
         self.lidar = None
         self.flow = None
+        self.frame_tags = None
         self.term_record = None
         self.term_obs = None
         self.bev = None
@@ -473,6 +540,11 @@ class FFMPVec:
             self.potential.zero_()  # the pairing probe wrote into it
         L = self.cfg.n_beams
         self.beam_cs = torch.as_tensor(beam_table(L), dtype=torch.float64).to(dev) if L > 0 else None
+        if self.frame_tags is not None:
+            if self.ring == "seamless":
+                self.invalidate_frame_tags()  # a ring's contents are undefined (new) or stale (kept)
+            else:
+                self.frame_tags.zero_()       # the frames were allocated as zeros: tag 0 holds
         self._note_hbm()
 
     @staticmethod
@@ -585,6 +657,7 @@ class FFMPVec:
         self._arena_buf = buf
         for n, v in views.items():
             setattr(self, n, v)
+        self.invalidate_frame_tags()  # a kept ring was written under the other arenas' tags
         self._build_structs()
         del keep, spacers, views, buf
         torch.cuda.empty_cache()
@@ -677,7 +750,7 @@ class FFMPVec:
                 break
             held.append(self._arena_buf)
             held.append(torch.empty((k + 1) * self.PLACEMENT_SPACER, dtype=torch.uint8, device=self.device))
-            self._ring = self.frames = None  # the best ring stays referenced by `best`
+            self._ring = self._frames = None  # the best ring stays referenced by `best`
             try:
                 self._alloc()
             except _abi.FFMPBackendError:
@@ -696,19 +769,21 @@ class FFMPVec:
         self._arena_buf, self._ring, self.ring = best["arena"], best["ring"], "seamless"
         for n, v in best["views"].items():
             setattr(self, n, v)
-        self.frames = self._ring.tensor
+        self._frames = self._ring.tensor
         self._arena_used = self._arena_buf.numel()
         torch.cuda.synchronize(self.device)
         del held
         self.potential.zero_()
-        self.frames[:self.frame_window].zero_()
+        self._frames[:self.frame_window].zero_()
+        self.invalidate_frame_tags()
         self.ring_meta = dict(best["meta"], partner_tries=[round(g, 1) for g in tries])
         best = None
         torch.cuda.empty_cache()
 
     def _adopt_ring_tensor(self) -> None:
-        self.frames = self._ring.tensor
+        self._frames = self._ring.tensor
         self.potential.zero_()
+        self.invalidate_frame_tags()  # rebuilt / reverted slots: other pieces, written by probes
         self._build_structs()
 
     def _repair_slots(self) -> None:
@@ -794,11 +869,17 @@ class FFMPVec:
         if self._arena_buf is not None:
             self._arena_buf.zero_()
         if self.ring == "seamless":
-            self.frames[:self.frame_window].zero_()
+            self._frames[:self.frame_window].zero_()
+        if self.frame_tags is not None:
+            if self._arena_buf is not None or self.ring == "seamless":
+                self.frame_tags.zero_()  # every frame was just zeroed: tag 0 holds for every granule
+            else:
+                self.invalidate_frame_tags()
         self._needs_reset = True
 
     def _autotune_raster(self) -> None:
         self.reset()  # a real state (a zeroed record would stack every disc on the robot cell)
+        self._warm_tags()
         results = []
         steps = self._tune_steps()
         for shape in self._shape_candidates():
@@ -869,13 +950,29 @@ class FFMPVec:
 
     XCD_SHAPES = True  # autotune candidates include the XCD-aware block remap
 
+    # With granule tags the 8-row tiles (32-cell row segments, half a granule) store every cell and
+    # leave tag 1 behind, which would also make the next candidate's first ring cycle dense: dropped.
     def _shape_candidates(self):
         shapes = self.COMPACT_SHAPES if self.obs_format == "u8f16" else self.RASTER_SHAPES
-        return [sh for sh in shapes if self.XCD_SHAPES or not sh[1] & _abi.RASTER_XCD]
+        return [sh for sh in shapes if (self.XCD_SHAPES or not sh[1] & _abi.RASTER_XCD)
+                and not (self.frame_tags is not None and sh[1] & _abi.RASTER_TILE8)]
 
     def _fused_candidates(self):
         flags = self.COMPACT_FUSED_FLAGS if self.obs_format == "u8f16" else self.FUSED_FLAGS
-        return [f for f in flags if self.XCD_SHAPES or not f & _abi.RASTER_XCD]
+        return [f for f in flags if (self.XCD_SHAPES or not f & _abi.RASTER_XCD)
+                and not (self.frame_tags is not None and f & _abi.RASTER_TILE8)]
+
+    def _warm_tags(self) -> None:
+        """One untimed ring cycle of real steps, so that every slot a timed step overwrites holds a
+        stepped frame with exact tags (after a reset the slots beyond the pair hold zeros or unknown
+        tags, and re-rastering one record would make old and new discs coincide: about half the
+        granules a real step stores).  The shape ranking, the placement check and the one- /
+        two-launch recheck then time the raster under the tags of the steady state."""
+        if self.frame_tags is None:
+            return
+        a = torch.full((self.num_envs,), 10, dtype=torch.int64, device=self.device)
+        for _ in range(self.frame_window):
+            self.step(a)
 
     def _tune_fused(self, steps: int) -> Optional[dict]:
         """Time whole steps of the two-launch path (the tuned raster shapes) against the fused
@@ -909,6 +1006,7 @@ class FFMPVec:
         if self._fused_req is not None or self.pipeline_slices > 1 or not tf:
             return
         self.reset()
+        self._warm_tags()
         steps = 2 * self._tune_steps()
         rounds = 2
         if max(tf.get("two_launch_step_ms", 1.0), tf.get("fused_step_ms", 1.0)) < self.SHORT_STEP_MS:
@@ -943,6 +1041,7 @@ class FFMPVec:
     def _placement_gbs(self) -> float:
         """Cycle bandwidth of the current buffers with the current launch shapes."""
         self.reset()
+        self._warm_tags()
         r = self._raster_gbs_steady(self._tune_steps())
         gbs = self._cycle_gbs(r[True][1] if True in r else None, r[False][1] if False in r else None)
         self._clear_after_tuning()
@@ -955,9 +1054,11 @@ class FFMPVec:
                                     self.episode.data_ptr(), self.record.data_ptr(), self.err.data_ptr(),
                                     _ptr(self.term_record), _ptr(self.term_obs))
         G2 = self.cfg.grid * self.cfg.grid
-        self._obs_c = _abi.ObsT(self.state_m.data_ptr(), self.state_g.data_ptr(), self.state_v.data_ptr(),
-                                self.state_t.data_ptr(), _ptr(self.potential), self.grad.data_ptr(),
-                                _ptr(self.lidar), _ptr(self.flow), *self._sm_strides(), self._fmt)
+        obs_t = _abi.ObsT if self.frame_tags is None else _abi.ObsTagsT
+        self._obs_c = obs_t(self.state_m.data_ptr(), self.state_g.data_ptr(), self.state_v.data_ptr(),
+                            self.state_t.data_ptr(), _ptr(self.potential), self.grad.data_ptr(),
+                            _ptr(self.lidar), _ptr(self.flow), *self._sm_strides(), self._fmt)
+        self._set_tags(self._wpos)
         self._out_c = _abi.OutT(self.reward.data_ptr(), self.done.data_ptr(), self.is_goal.data_ptr(),
                                 self.collision.data_ptr(), self.truncated.data_ptr())
         self._build_slices()
@@ -999,17 +1100,20 @@ class FFMPVec:
     # ------------------------------------------------------------ frame window
     @property
     def state_m(self) -> torch.Tensor:
-        """(N, 2, G, G) [older, newest] view of the frame window (contiguous iff W == 2)."""
+        """(N, 2, G, G) [older, newest] view of the frame window (contiguous iff W == 2).
+        Read-only for consumers, like `frames`: with sparse_frames the raster skips stores into
+        granules it knows to be zero, so a caller that writes into the ring must call
+        invalidate_frame_tags() before the next step."""
         if self.frame_window == 2:
-            return self.frames
-        return self.frames[self._wpos:self._wpos + 2].transpose(0, 1)
+            return self._frames
+        return self._frames[self._wpos:self._wpos + 2].transpose(0, 1)
 
     def _sm_strides(self):
         """(env stride, frame stride) of state_m in elements, for ffmp_obs_t."""
         G2 = self.cfg.grid * self.cfg.grid
         if self.frame_window == 2:
             return (2 * G2, G2)
-        return (G2, self.frames.stride(0))
+        return (G2, self._frames.stride(0))
 
     # Seamless ring, wrap step (pair [W-1, W]): the newest frame goes to physical slot 0, which
     # virtual slots 0 and W both map.  WRAP_VIA_ALIAS False: the raster writes it through slot
@@ -1017,11 +1121,25 @@ class FFMPVec:
     # through slot W.  Same bytes either way.
     WRAP_VIA_ALIAS = True
 
+    def _set_tags(self, p: int) -> None:
+        """Point the launch struct at the tags of the PHYSICAL slots of the pair [p, p + 1]: the
+        seamless ring's virtual slot W is slot 0 (through the alias or the negative frame stride
+        alike); the wrapping ring and the contiguous pair never leave [0, slots)."""
+        tg = self.frame_tags
+        if tg is None:
+            return
+        o, slots = self._obs_c, tg.shape[0]
+        o.reserved = _abi.OBS_EXT_TAGS
+        o.tags_older = tg.data_ptr() + (p % slots) * tg.stride(0)
+        o.tags_newest = tg.data_ptr() + ((p + 1) % slots) * tg.stride(0)
+        o.tags_env_stride = tg.stride(1)
+
     def _set_window(self, p: int) -> None:
         self._wpos = p
-        self._obs_c.state_m = self.frames.data_ptr() + p * self.frames.stride(0) * self._fes
+        self._set_tags(p)
+        self._obs_c.state_m = self._frames.data_ptr() + p * self._frames.stride(0) * self._fes
         if self.ring == "seamless":
-            W, fs = self.frame_window, self.frames.stride(0)
+            W, fs = self.frame_window, self._frames.stride(0)
             wrap = p == W - 1 and not self.WRAP_VIA_ALIAS
             self._obs_c.state_m_frame_stride = -(W - 1) * fs if wrap else fs
 
@@ -1136,16 +1254,16 @@ class FFMPVec:
                                    f"temporal_maps({k}) needs {k} (step {k - len(self._hist)} more times, or reset())")
             # lags the ring has not seen since a full reset are never read (every env's lag is
             # clamped to its steps since that reset): any valid slot stands in
-            offs = [self._hist[min(d, len(self._hist) - 1)] * self.frames.stride(0) for d in range(k)]
+            offs = [self._hist[min(d, len(self._hist) - 1)] * self._frames.stride(0) for d in range(k)]
             env_stride = G * G
         offs = (offs + [offs[-1]] * k)[:k]
         if out is None:
-            out = torch.empty(N, k, G, G, dtype=self.frames.dtype, device=self.device)
-        elif out.shape != (N, k, G, G) or out.dtype != self.frames.dtype or not out.is_contiguous() \
+            out = torch.empty(N, k, G, G, dtype=self._frames.dtype, device=self.device)
+        elif out.shape != (N, k, G, G) or out.dtype != self._frames.dtype or not out.is_contiguous() \
                 or out.device != self.device:
-            raise ValueError(f"out must be a contiguous {self.frames.dtype} tensor of shape {(N, k, G, G)} on {self.device}")
+            raise ValueError(f"out must be a contiguous {self._frames.dtype} tensor of shape {(N, k, G, G)} on {self.device}")
         lag = (C.c_int64 * k)(*offs)
-        _abi.check(self.lib.ffmp_temporal_maps(N, self.frames.data_ptr(), lag, k, env_stride, G * G, self._fes,
+        _abi.check(self.lib.ffmp_temporal_maps(N, self._frames.data_ptr(), lag, k, env_stride, G * G, self._fes,
                                                self.t.data_ptr(), out.data_ptr(), self._stream()), "ffmp_temporal_maps")
         return out
 
@@ -1308,6 +1426,11 @@ class FFMPVec:
         """Re-raster the current observation (both frames, potential, flow) from the record."""
         self._check_open()
         m = None if mask is None else mask.to(device=self.device, dtype=torch.bool).contiguous().view(torch.uint8)
+        if self.frame_tags is not None:
+            # an explicit re-raster rewrites the pair whatever it holds (a reloaded checkpoint, a
+            # caller that wrote into state_m): no store of it is skipped
+            slots = self.frame_tags.shape[0]
+            self.invalidate_frame_tags([self._wpos % slots, (self._wpos + 1) % slots])
         self._raster_launch(True, m)
         self._bev_push(advance=False)
 
@@ -1825,7 +1948,7 @@ class FFMPVec:
         if self._arena_buf is not None:
             return self._arena_buf.numel() + ring + (0 if alt is None else alt.numel() * alt.element_size())
         return ring + sum(t.numel() * t.element_size() for t in vars(self).values()
-                          if isinstance(t, torch.Tensor) and not (ring and t is self.frames))
+                          if isinstance(t, torch.Tensor) and not (ring and t is self._frames))
 
     def __repr__(self):
         c = self.cfg

@@ -164,8 +164,45 @@ typedef struct ffmp_obs {
                                    newest frame in a lower slot: a seamless ring's wrap step can
                                    write slot 0 through its first mapping instead of slot W's). */
   int32_t format;   /* FFMP_OBS_F32 (0) or FFMP_OBS_U8F16 */
-  int32_t reserved;
+  int32_t reserved; /* 0, or FFMP_OBS_EXT_* bits: what follows this struct in memory (below) */
 } ffmp_obs_t;
+
+/* Sparse frame stores (an addition within ABI 9: no existing symbol, struct size or value changes).
+ * An occupancy frame is 0 outside the discs and the world's walls, and so is the frame the ring slot
+ * held before, so almost every 16-byte frame store of a step writes 0.0f over 0.0f.  With granule
+ * tags the raster skips those stores; every frame, plane and record word stays what the dense raster
+ * writes.
+ *   reserved == 0: today's behaviour, the ffmp_obs_t stands alone.
+ *   reserved & FFMP_OBS_EXT_TAGS: the ffmp_obs_t* passed in points at the first member of an
+ *   ffmp_obs_tags_t.  Read by every launch that rasters: ffmp_raster, ffmp_raster_ex, ffmp_step,
+ *   ffmp_step_cmd, ffmp_step_fused, ffmp_step_fused_cmd, ffmp_step_skewed; ignored by the others.
+ * A granule is 64 consecutive cells of a frame plane in linear order (cell q is in granule q / 64; the
+ * last one of a plane may be partial), one tag byte per granule: T = ceil(G*G / 64) tags per frame.
+ *   tags_older / tags_newest: the tags of the frames state_m[:, 0] / state_m[:, 1] address, env 0's
+ *   first; env e's are tags_env_stride bytes further per env (>= T).  They belong to the MEMORY of a
+ *   frame (a physical ring slot), not to the view: a slot mapped at two addresses (the seamless ring's
+ *   slot 0) has one set of tags.  Device memory, no alignment.
+ * Invariant: tag == 0  =>  all cells of that granule of that frame are 0.0f (+0).  tag == 1: unknown
+ * or non-zero.  Any other value counts as 1.
+ * Per frame it writes (the newest one; the older one too where it writes it), a launch stores a
+ * granule's cells only if one of them is non-zero or the granule's tag is non-zero, and then sets the
+ * tag to "one of them is non-zero".  Launch shapes whose store groups are not whole granules
+ * (FFMP_RASTER_TILE8 / TILE16) and blocks of more than 65,536 cells store everything and write tag 1.
+ * An env a launch skips (mask) keeps its cells and its tags.
+ * Who may write a tagged frame: the launches above, through an ffmp_obs_tags_t that names the frame's
+ * tags.  For every consumer the frames are read-only.  A caller that writes frame memory itself (a
+ * memset, a copy, a launch without the flag, memory that is new or re-mapped) must set the tags of the
+ * frames it touched to 1 before the next tagged launch; all-zero memory may take tags 0 instead.
+ * FFMP_E_ARG (nothing launched): the flag with a NULL tag pointer, with tags_env_stride < T, or with
+ * format != FFMP_OBS_F32 (the compact frames are stored densely). */
+#define FFMP_OBS_EXT_TAGS 1
+#define FFMP_TAG_CELLS 64
+typedef struct ffmp_obs_tags {
+  ffmp_obs_t obs;          /* obs.reserved & FFMP_OBS_EXT_TAGS */
+  uint8_t* tags_older;     /* (N, T) tags of the frame at state_m */
+  uint8_t* tags_newest;    /* (N, T) tags of the frame at state_m + state_m_frame_stride */
+  int64_t tags_env_stride; /* bytes between consecutive envs' tags, >= T */
+} ffmp_obs_tags_t;
 
 /* Per-step outputs (device pointers, N each). Flags are 0/1 bytes. */
 typedef struct ffmp_out {
@@ -183,7 +220,8 @@ const char* ffmp_last_error(void);
  * 2 sizeof(ffmp_obs_t), 3 sizeof(ffmp_out_t), 4 offsetof(ffmp_cfg_t, res),
  * 5 offsetof(ffmp_cfg_t, res_f), 6 offsetof(ffmp_cfg_t, seed),
  * 7 offsetof(ffmp_cfg_t, beam_cs), 8 sizeof(ffmp_episode_t),
- * 9 offsetof(ffmp_obs_t, format); -1 otherwise. */
+ * 9 offsetof(ffmp_obs_t, format); the extension structs from 20 on: 20 sizeof(ffmp_obs_tags_t),
+ * 21 offsetof(ffmp_obs_tags_t, tags_older); -1 otherwise (10 .. 19 included). */
 int64_t ffmp_layout(int32_t which);
 
 /* Launch-shape tuning (process-wide; not thread-safe against concurrent launches).
