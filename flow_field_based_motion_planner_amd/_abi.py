@@ -138,6 +138,11 @@ _SIGS = {
     "ffmp_nav_field": (C.c_int, [C.POINTER(CfgT), _I64, C.POINTER(ObsT), _P, _I64, _I32, _I32, _I32, C.c_double,
                                  _P, _P, _P, _P, _P, _P]),
     "ffmp_nav_field_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32]),
+    # the same on grids up to 512 x 512: tiles through LDS, the plane and the masks in a workspace
+    "ffmp_nav_field_tiled": (C.c_int, [C.POINTER(CfgT), _I64, C.POINTER(ObsT), _P, _I64, _I32, _I32, _I32, C.c_double,
+                                       _P, _P, _P, _P, _P, _I32, _P, C.c_size_t, _P]),
+    "ffmp_nav_field_tiled_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, _I32]),
+    "ffmp_nav_field_tiled_workspace": (C.c_int, [C.POINTER(CfgT), _I64, _I32, C.c_int, C.POINTER(C.c_size_t)]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

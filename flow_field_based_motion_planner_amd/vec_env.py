@@ -1664,14 +1664,62 @@ class FFMPVec:
     # ------------------------------------------------ navigation field
     NAV_DEFAULTS = dict(margin=2, soft_pen=40, lookahead=4, turn_sin=0.25)
 
+    nav_tile: Optional[int] = None  # set (0 = the library's default tile) to plan through the tiled kernel on any grid
+    _nav_ws = None                  # (tile, with_cost) -> the tiled kernel's workspace, a device tensor
+
+    def _nav_tiled(self, tile: Optional[int]) -> Optional[int]:
+        """The tile of the tiled kernel (ffmp_nav_field_tiled; 0 = its default), or None for the
+        kernel that holds the whole plane in LDS: tiled when `tile` or the attribute nav_tile is
+        given, or when the grid is larger than 256 x 256."""
+        if tile is None:
+            tile = self.nav_tile
+        if tile is None:
+            return 0 if self.cfg.grid > 256 else None
+        return int(tile)
+
+    def _nav_workspace(self, tile: int, with_cost: bool) -> torch.Tensor:
+        """The workspace of the tiled kernel for this env count, allocated on first use and kept
+        until close(), per (tile, with_cost)."""
+        if self._nav_ws is None:
+            self._nav_ws = {}
+        key = (tile, bool(with_cost))
+        ws = self._nav_ws.get(key)
+        if ws is None:
+            nbytes = C.c_size_t()
+            with torch.cuda.device(self.device):
+                _abi.check(self.lib.ffmp_nav_field_tiled_workspace(C.byref(self._cfg_c), self.num_envs, tile, int(with_cost),
+                                                                   C.byref(nbytes)), "ffmp_nav_field_tiled_workspace")
+            buf = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self.device)
+            off = (-buf.data_ptr()) % 256
+            ws = self._nav_ws[key] = buf[off:off + nbytes.value]
+        return ws
+
+    def nav_workspace_bytes(self) -> int:
+        """Device bytes held by the tiled navigation kernel's workspaces (0 before the first tiled
+        call; freed by close())."""
+        return sum(int(ws.numel()) for ws in (self._nav_ws or {}).values())
+
     def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
-                    cost=None, direction=None, target=None, geo_cost=None, cmd=None) -> None:
-        """One ffmp_nav_field launch over the current observation: the newest frame through the
-        window's strides and format, the ego goal from record words 8..9."""
+                    cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None) -> None:
+        """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
+        observation: the newest frame through the window's strides and format, the ego goal from
+        record words 8..9."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError(f"call reset() before {what}()")
         knobs = (int(margin), int(soft_pen), int(lookahead))
+        tile = self._nav_tiled(tile)
+        if tile is not None:
+            _abi.check(self.lib.ffmp_nav_field_tiled_check(C.byref(self._cfg_c), self._fmt, *knobs, tile),
+                       "ffmp_nav_field_tiled_check")
+            ws = self._nav_workspace(tile, cost is not None)
+            with torch.cuda.device(self.device):
+                _abi.check(self.lib.ffmp_nav_field_tiled(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
+                                                         self.record.data_ptr() + 8 * 4, self.record.stride(0), *knobs,
+                                                         float(turn_sin), _ptr(cost), _ptr(direction), _ptr(target),
+                                                         _ptr(geo_cost), _ptr(cmd), tile, ws.data_ptr(), ws.numel(),
+                                                         self._stream()), "ffmp_nav_field_tiled")
+            return
         _abi.check(self.lib.ffmp_nav_field_check(C.byref(self._cfg_c), self._fmt, *knobs), "ffmp_nav_field_check")
         with torch.cuda.device(self.device):
             _abi.check(self.lib.ffmp_nav_field(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
@@ -1680,7 +1728,7 @@ class FFMPVec:
                                                _ptr(geo_cost), _ptr(cmd), self._stream()), "ffmp_nav_field")
 
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
-                  lookahead: int = 4) -> Dict[str, torch.Tensor]:
+                  lookahead: int = 4, tile: Optional[int] = None) -> Dict[str, torch.Tensor]:
         """The navigation field of the current observation, on the device (include/ffmp.h
         ffmp_nav_field): the cost-to-go from the goal cell over the traversable cells of the newest
         ego frame (hard = the footprint-dilated occupancy; a `margin`-cell zone around it costs
@@ -1692,7 +1740,12 @@ class FFMPVec:
                    ~8 %), with the zone's penalties included
           cost (N, G, G) uint16 (65535: hard or unreachable) with cost=True
           dir  (N, G, G) uint8 (neighbour index 0..7, 8 at the goal, 255 unreachable) with direction=True
-        A static plan: obstacle velocities are not looked at.  Grids up to 256 x 256."""
+        A static plan: obstacle velocities are not looked at.  Grids up to 512 x 512: up to
+        256 x 256 one workgroup holds an env's whole plane in LDS; above that, or when `tile` (or the
+        attribute nav_tile) is given, the plane lives in a workspace on the device and is relaxed in
+        tiles of `tile` x `tile` cells (0 = the library's default, 256; else a multiple of 32 in
+        [32, 256]) — the same bits either way (include/ffmp.h ffmp_nav_field_tiled).  The workspace
+        is allocated on the first such call and kept until close() (nav_workspace_bytes())."""
         n, G = self.num_envs, self.cfg.grid
         out = {"target": torch.empty((n, 2), dtype=torch.int32, device=self.device),
                "geo_cost": torch.empty(n, dtype=torch.int32, device=self.device)}
@@ -1701,20 +1754,22 @@ class FFMPVec:
         if direction:
             out["dir"] = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
         self._nav_launch("nav_field", margin, soft_pen, lookahead, self.NAV_DEFAULTS["turn_sin"],
-                         cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"])
+                         cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"],
+                         tile=tile)
         gc = out["geo_cost"].to(torch.float64)
         out["geo_dist"] = torch.where(gc < 0, torch.full_like(gc, float("inf")), gc * (self.cfg.res / 5.0))
         return out
 
     def policy_nav(self, out: Optional[torch.Tensor] = None, margin: int = 2, soft_pen: int = 40, lookahead: int = 4,
-                   turn_sin: float = 0.25) -> torch.Tensor:
+                   turn_sin: float = 0.25, tile: Optional[int] = None) -> torch.Tensor:
         """The next (v, w) commands (N, 2) float64 from the navigation field of the current
         observation, on the device (include/ffmp.h ffmp_nav_field's follower): head for the cell
         `lookahead` moves down the cheapest path, turning on the spot while it lies more than
         asin(turn_sin) off the heading.  Complete on a static scene (it has no local minima, unlike
         policy_field); stateless, so on an exactly symmetric scene it can dither between two equal
         routes; obstacle velocities are not looked at.  (0, 0) when the goal is unreachable.  `out`:
-        write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one."""
+        write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one.  `tile`: as
+        for nav_field (grids above 256 x 256 always take the tiled kernel)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_nav()")
@@ -1724,7 +1779,7 @@ class FFMPVec:
                 or out.device != self.device or out.data_ptr() % 16:
             raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
                              f"({self.num_envs}, 2) on {self.device}")
-        self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out)
+        self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out, tile=tile)
         return out
 
     # ------------------------------------------------ HIP graph of whole steps
@@ -1864,6 +1919,7 @@ class FFMPVec:
         self._slices = []
         self._arena_buf = None
         self._record_alt = None
+        self._nav_ws = None
         self.bev = None
         had_ring = self.ring == "seamless"
         self._ring = None  # the seamless ring's pieces return to the process pool ...
@@ -2068,6 +2124,8 @@ class StepGraph:
         self.wpos = env._wpos
         self.graph = torch.cuda.CUDAGraph()
         stream = torch.cuda.Stream(device=env.device)
+        if policy == "nav" and env._nav_tiled(None) is not None:
+            env._nav_workspace(env._nav_tiled(None), False)  # allocated before the capture: the graph holds its pointer
         torch.cuda.synchronize(env.device)
         rec0 = env.record
         if self.pipelined or self.skewed:

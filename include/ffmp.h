@@ -479,6 +479,39 @@ int ffmp_nav_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs,
                    double* cmd /* (n,2), 16-B aligned, or NULL */, void* stream);
 int ffmp_nav_field_check(const ffmp_cfg_t* cfg, int32_t format, int32_t margin, int32_t soft_pen, int32_t lookahead);
 
+/* The same field on grids up to 512 x 512 (an addition within ABI 9: no existing symbol, struct or
+ * value changes): the SPEC above ffmp_nav_field, every output bit for bit what it defines — the
+ * fixed point is unique, so the tiling does not show.  8 <= G <= 512, G % 4 == 0.
+ * Tiling: the cost plane of an env lives in global memory (the caller's cost + e G^2 when cost is
+ * given, else in the workspace) and is relaxed a tile of `tile` x `tile` cells at a time through
+ * LDS, each tile with a one-cell halo that is read and never relaxed; a tile whose border changed
+ * makes the neighbours that see the change due again, until no tile is due.  tile: 0 = the default,
+ * 256; otherwise a multiple of 32 in [32, 256] (a tile larger than the grid is cut to it).
+ * Schedule: a persistent grid of `slots` workgroups, workgroup b planning envs b, b + slots, ...;
+ * slots = min(n, CUs x resident workgroups per CU), at most 2048.  No workgroup waits on another.
+ * Workspace: DEVICE memory, 256-byte aligned, slots x per-slot bytes — per slot the hard and soft
+ * masks of the grid (2 x G x ceil(G / 32) words, rounded up to 256 bytes) and, when cost is NULL,
+ * a plane of G^2 uint16 (rounded likewise).  ffmp_nav_field_tiled_workspace writes that product to
+ * *bytes for the current device, the same slot count the launch uses; with_cost != 0: the calls
+ * will pass cost.  Without a HIP device it answers with the bound min(n, 2048) slots.  The contents
+ * need not survive between calls; calls that may run concurrently need a workspace each.
+ * FFMP_E_ARG, with a message and before any HIP call, for: everything ffmp_nav_field refuses (with
+ * the grid range above); a tile that is neither 0 nor a multiple of 32 in [32, 256]; workspace NULL,
+ * not 256-byte aligned, or smaller than one slot (smaller than slots x per-slot bytes: refused once
+ * the device's slot count is known, before the launch).  n == 0: nothing is launched.
+ * ffmp_nav_field_tiled_check: the checks that need no pointer (shape, format, knobs, tile, LDS
+ * budget), no launch. */
+int ffmp_nav_field_tiled(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs,
+                         const float* goal_ego, int64_t goal_stride /* floats between envs */,
+                         int32_t margin, int32_t soft_pen, int32_t lookahead, double turn_sin,
+                         uint16_t* cost /* (n,G,G) or NULL */, uint8_t* dir /* (n,G,G) or NULL */,
+                         int32_t* target /* (n,2) or NULL */, int32_t* geo_cost /* (n) or NULL */,
+                         double* cmd /* (n,2), 16-B aligned, or NULL */,
+                         int32_t tile, void* workspace, size_t workspace_bytes, void* stream);
+int ffmp_nav_field_tiled_check(const ffmp_cfg_t* cfg, int32_t format, int32_t margin, int32_t soft_pen, int32_t lookahead,
+                               int32_t tile);
+int ffmp_nav_field_tiled_workspace(const ffmp_cfg_t* cfg, int64_t n, int32_t tile, int with_cost, size_t* bytes);
+
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
  *   local_map: float32 planes, env e at local_map + e*map_stride (G x G), or NULL

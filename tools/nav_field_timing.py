@@ -9,10 +9,17 @@ interleaved:
     step            step(actions) — the env step the field is quoted against
     nav_cmd         ffmp_nav_field writing cmd only (policy_nav into a preallocated tensor)
     nav_planes      ffmp_nav_field writing the cost and dir planes (+ target, geo_cost)
-Appends one JSON line per config to profiles/nav_field_timing.jsonl (--out) and prints it.  The field
-is opt-in and off the hot path: a record, no threshold.
+With --tile T (0 = the library's default tile), and always on a grid above 256 x 256, the tiled kernel
+(ffmp_nav_field_tiled: the plane in HBM, tiles through LDS) is timed as well, on the same frames:
+    nav_cmd_tiled, nav_planes_tiled
+so that at C3 with --tile 256 (one tile per env) the two kernels stand side by side: the difference
+is the cost of going through HBM.  "C5share" is C5's share of one GPU, 16,384 x 512^2.
+Appends one JSON line per config to profiles/nav_field_timing.jsonl (--out; by default
+profiles/nav_field_tiled_timing.jsonl when a tiled kind is timed) and prints it.  The field is opt-in
+and off the hot path: a record, no threshold.
 
     python tools/nav_field_timing.py [--configs C2,C3] [--calls 5] [--repeats 3] [--envs N]
+    python tools/nav_field_timing.py --configs C5share,C3 --tile 256
 """
 import argparse
 import json
@@ -30,16 +37,22 @@ def main():
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=3, help="timed regions per kind, interleaved; all are reported")
     ap.add_argument("--envs", type=int, default=0, help="override the preset's env count")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "nav_field_timing.jsonl"))
+    ap.add_argument("--tile", type=int, default=None, help="also time the tiled kernel with this tile (0 = its default)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
     from flow_field_based_motion_planner_amd.config import PRESETS, preset
     from flow_field_based_motion_planner_amd.vec_env import FFMPVec
 
+    shares = {"C5share": ("C5", 16384)}  # a multi-GPU preset's share of one GPU
     for name in args.configs.split(","):
-        n = args.envs or PRESETS[name]["n_envs"]
-        env = FFMPVec(n, preset(name), device="cuda:0", autotune=False)
+        base, share = shares.get(name, (name, 0))
+        n = args.envs or share or PRESETS[base]["n_envs"]
+        env = FFMPVec(n, preset(base), device="cuda:0", autotune=False)
         G = env.cfg.grid
+        tile = args.tile if args.tile is not None else (0 if G > 256 else None)
+        out_path = args.out or os.path.join(ROOT, "profiles", "nav_field_timing.jsonl" if tile is None
+                                            else "nav_field_tiled_timing.jsonl")
         env.reset()
         for _ in range(8):
             env.step(env.policy_reactive())
@@ -50,9 +63,15 @@ def main():
         dirs = torch.empty((n, G, G), dtype=torch.uint8, device=env.device)
         target = torch.empty((n, 2), dtype=torch.int32, device=env.device)
         geo = torch.empty(n, dtype=torch.int32, device=env.device)
-        kinds = {"step": lambda: env.step(actions),
-                 "nav_cmd": lambda: env._nav_launch("nav_field", **kn, cmd=cmd),
-                 "nav_planes": lambda: env._nav_launch("nav_field", **kn, cost=cost, direction=dirs, target=target, geo_cost=geo)}
+        kinds = {"step": lambda: env.step(actions)}
+        if G <= 256:
+            kinds["nav_cmd"] = lambda: env._nav_launch("nav_field", **kn, cmd=cmd)
+            kinds["nav_planes"] = lambda: env._nav_launch("nav_field", **kn, cost=cost, direction=dirs, target=target,
+                                                          geo_cost=geo)
+        if tile is not None:
+            kinds["nav_cmd_tiled"] = lambda: env._nav_launch("nav_field", **kn, cmd=cmd, tile=tile)
+            kinds["nav_planes_tiled"] = lambda: env._nav_launch("nav_field", **kn, cost=cost, direction=dirs, target=target,
+                                                                geo_cost=geo, tile=tile)
 
         def timed(body, k):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -71,14 +90,21 @@ def main():
         med = {key: sorted(ts)[len(ts) // 2] for key, ts in runs.items()}
         reach = int((geo >= 0).sum())
         out = {"config": name, "n_envs": n, "grid": G, "n_obst": env.cfg.n_obst, "calls": args.calls, "warm": args.warm,
-               "knobs": kn, "reachable_envs": reach, "ms_per_call": runs,
-               "nav_cmd_over_step": round(med["nav_cmd"] / med["step"], 2),
-               "nav_planes_over_step": round(med["nav_planes"] / med["step"], 2)}
+               "knobs": kn, "reachable_envs": reach, "ms_per_call": runs}
+        for key in kinds:
+            if key != "step":
+                out[key + "_over_step"] = round(med[key] / med["step"], 2)
+        if tile is not None:
+            out["tile"] = tile
+            out["workspace_bytes"] = env.nav_workspace_bytes()
+            if "nav_cmd" in kinds:
+                out["tiled_over_untiled"] = {"cmd": round(med["nav_cmd_tiled"] / med["nav_cmd"], 3),
+                                             "planes": round(med["nav_planes_tiled"] / med["nav_planes"], 3)}
         env.check_errors()
         line = json.dumps(out)
         print(line, flush=True)
-        os.makedirs(os.path.dirname(args.out), exist_ok=True)
-        with open(args.out, "a") as f:
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "a") as f:
             f.write(line + "\n")
         env.close()
         del env, kinds, cost, dirs
