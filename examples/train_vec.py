@@ -66,6 +66,9 @@ def main():
                          "12 = (occupancy + RGB flow) x 3 steps (FFMPVec.bev_maps); with --temporal-maps: that many frames")
     ap.add_argument("--temporal-maps", action="store_true",
                     help="make_temporal_maps over --input-channels mono frames (train.py:474-486), from the frame ring")
+    ap.add_argument("--visible", action="store_true",
+                    help="act and learn on the sensor-visible frames (FFMPVec.visible_frames: cells an obstacle "
+                         "hides from the robot read 128) instead of the ground-truth pair")
     ap.add_argument("--warmup", type=int, default=3, help="untimed loop iterations (MIOpen compiles each conv shape once)")
     args = ap.parse_args()
     if args.reference_hparams:
@@ -83,7 +86,7 @@ def main():
     brain = Brain(env, capacity=args.capacity, batch_size=args.batch, seed=args.seed, amp=args.amp,
                   mfma=False if args.no_mfma else None,
                   channels_last=args.channels_last, input_channels=args.input_channels,
-                  temporal_maps=args.temporal_maps)
+                  temporal_maps=args.temporal_maps, visible={} if args.visible else None)
     obs = env.reset()
     tracker = EpisodeTracker(args.envs, device=dev)
     losses, updates = [], 0
@@ -122,7 +125,7 @@ def main():
            "updates_per_s": timed_updates / dt, "conv_tflops_per_s": conv_flop / dt / 1e12,
            "conv_gflop_per_sample": {k: round(v / 1e9, 3) for k, v in fl.items()},
            "envs": args.envs, "steps": args.steps, "amp": args.amp, "mfma": bool(brain.mfma and args.amp), "channels_last": args.channels_last,
-           "input_channels": args.input_channels, "temporal_maps": args.temporal_maps,
+           "input_channels": args.input_channels, "temporal_maps": args.temporal_maps, "visible": args.visible,
            "learner_updates": updates, "batch": args.batch, "loss_samples": losses[:10],
            "replay_bytes": brain.memory.hbm_bytes(), "replay_len": len(brain.memory), **summ}
     print(json.dumps(out))

@@ -143,6 +143,10 @@ _SIGS = {
                                        _P, _P, _P, _P, _P, _I32, _P, C.c_size_t, _P]),
     "ffmp_nav_field_tiled_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, _I32]),
     "ffmp_nav_field_tiled_workspace": (C.c_int, [C.POINTER(CfgT), _I64, _I32, C.c_int, C.POINTER(C.c_size_t)]),
+    # sensor-visible occupancy frames (an addition within ABI 9): the raster with line of sight applied
+    "ffmp_visible_frames": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P, _P, _I64, _I32, _I32, C.c_float, _I32,
+                                      _P]),
+    "ffmp_visible_frames_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, C.c_float, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),
@@ -253,6 +257,7 @@ RASTER_TILE2, RASTER_TILE4, RASTER_TILE8 = 16, 32, 64
 RASTER_NARROW = 128  # FFMP_OBS_U8F16: 4 cells per lane instead of 16
 RASTER_TILE16 = 256
 RASTER_MID8 = 512  # FFMP_OBS_U8F16: 8 cells per lane
+VISIBLE_NOCULL = 1  # FFMP_VISIBLE_NOCULL: ffmp_visible_frames without its culls (the same bits)
 
 
 def set_tuning(key: int, value: int) -> int:

@@ -384,6 +384,14 @@ class FFMP(GymEnvBase):
                 out[k] = d[k][0].cpu().numpy()
         return out
 
+    def visible_frames(self, **kw):
+        """What a sensor at the robot can see of the frame pair (FFMPVec.visible_frames, include/ffmp.h
+        ffmp_visible_frames) of this one env, as a NumPy array: (2, G, G) [older, newest], or (G, G)
+        with newest_only=True; cells an obstacle hides hold `unknown` (default 128)."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before visible_frames()")
+        return self._vec_env().visible_frames(**kw)[0].cpu().numpy()
+
     def render(self, mode="human"):
         return None
 

@@ -53,7 +53,8 @@ class Brain:
     def __init__(self, env, capacity: int = CAPACITY, batch_size: int = BATCH_SIZE, gamma: float = GAMMA,
                  lr: float = LEARNING_RATE, replay_coupling: str = "reference", mask_terminal: bool = False,
                  seed: int = 0, amp: bool = False, channels_last: bool = False,
-                 input_channels: int = INPUT_CHANNELS, mfma: Optional[bool] = None, temporal_maps: bool = False):
+                 input_channels: int = INPUT_CHANNELS, mfma: Optional[bool] = None, temporal_maps: bool = False,
+                 visible: Optional[dict] = None):
         self.env = env
         self.device = env.device
         self.num_actions = NUM_ACTIONS
@@ -84,7 +85,13 @@ class Brain:
             if self.input_channels not in (1, 2, 3):
                 raise ValueError("input_channels must be 1, 2 or 3")
         series = 3 if self.bev else self.input_channels if self.temporal_maps else 2
-        self.memory = ReplayMemory(env, max(int(capacity), env.num_envs), seed=seed, series=series, bev=self.bev)
+        # visible: act and learn on what the robot's sensor can see (FFMPVec.visible_frames; a dict of
+        # its unknown / max_range, {} for the defaults) instead of the ground-truth frames
+        self.visible = None if visible is None else dict(visible)
+        if self.visible is not None and (self.temporal_maps or self.bev or self.input_channels != 2):
+            raise ValueError("visible needs the [older, newest] pair: input_channels=2 without temporal_maps")
+        self.memory = ReplayMemory(env, max(int(capacity), env.num_envs), seed=seed, series=series, bev=self.bev,
+                                   visible=self.visible)
         g = env.cfg.grid
         with torch.random.fork_rng(devices=[]):  # seeded init without touching the caller's RNG
             torch.manual_seed(seed)
@@ -127,6 +134,8 @@ class Brain:
             obs = dict(obs, state_m=self.env.temporal_maps(self.input_channels))
         elif self.bev:
             obs = dict(obs, state_m=self.env.bev_maps(3))
+        elif self.visible is not None:
+            obs = dict(obs, state_m=self.env.visible_frames(**self.visible))
         epsilon = 0.5 * (1.0 / (episode.to(torch.float64) + 1.0))
         u = torch.rand(n, generator=self.gen, device=self.device, dtype=torch.float64)
         self.main_q_network.eval()

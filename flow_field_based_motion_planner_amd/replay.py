@@ -56,9 +56,12 @@ class ReplayMemory:
     """Ring buffer of `capacity` transitions of `env` (an FFMPVec built with keep_terminal=True).
 
     sample() materialises the map stacks with the env's raster kernel (state_m / observe_m
-    f32 (B,2,G,G); with `potential=True` also the potential planes (B,G,G) of both sides)."""
+    f32 (B,2,G,G); with `potential=True` also the potential planes (B,G,G) of both sides).
+    visible=dict(unknown=..., max_range=...): the map stacks are the sensor-visible frames of the
+    stored records instead (FFMPVec.visible_frames; series=2, bev=False only)."""
 
-    def __init__(self, env, capacity: int, seed: int = 0, series: int = 2, bev: bool = False):
+    def __init__(self, env, capacity: int, seed: int = 0, series: int = 2, bev: bool = False,
+                 visible: Optional[dict] = None):
         if not getattr(env, "keep_terminal", False):
             raise ValueError("ReplayMemory needs FFMPVec(..., keep_terminal=True) (terminal records of done envs)")
         if capacity < env.num_envs:
@@ -78,6 +81,16 @@ class ReplayMemory:
         if not 1 <= self.series <= _abi.MAX_SERIES:
             raise ValueError(f"series must be in [1, {_abi.MAX_SERIES}]")
         self.bev = bool(bev)
+        # visible = dict(unknown=..., max_range=...) ({}: the defaults of FFMPVec.visible_frames):
+        # sample()'s state_m / observe_m are the sensor-visible frames of the stored records
+        # (include/ffmp.h ffmp_visible_frames), float32 as the ground-truth ones
+        self.visible = None if visible is None else dict(visible)
+        if self.visible is not None:
+            if self.series != 2 or self.bev:
+                raise ValueError("visible needs series=2, bev=False (the [older, newest] pair)")
+            extra = set(self.visible) - {"unknown", "max_range"}
+            if extra:
+                raise ValueError(f"visible takes unknown and max_range, got {sorted(extra)}")
         if self.bev and not self.cfg.flow:
             raise ValueError("bev=True needs an env with FFMPConfig(flow=True)")
         # the mono series' oldest frame is the older frame of record r_t-k+2; a BEV image needs
@@ -281,6 +294,13 @@ class ReplayMemory:
             o_recs = torch.cat((o_rec.unsqueeze(1), s_rec.unsqueeze(1), hist[:, :-1]), 1)  # r_t+1 .. r_t-k+3
             self._raster_series(s_recs, s_since, s_sm, s_pot, s_flow)
             self._raster_series(o_recs, s_since + 1, o_sm, o_pot, o_flow)
+        elif self.visible is not None:
+            for rec, sm, pot, flow in ((s_rec, s_sm, s_pot, s_flow), (o_rec, o_sm, o_pot, o_flow)):
+                if pot is not None or flow is not None:  # those planes are the ground truth's, unchanged
+                    self._raster(rec, sm, pot, flow)
+                G2 = self.cfg.grid * self.cfg.grid
+                self.env._visible_launch(rec, sm.data_ptr(), sm.data_ptr() + G2 * sm.element_size(), 2 * G2, _abi.OBS_F32,
+                                         self.visible.get("unknown", 128), self.visible.get("max_range"))
         else:
             self._raster(s_rec, s_sm, s_pot, s_flow)
             self._raster(o_rec, o_sm, o_pot, o_flow)

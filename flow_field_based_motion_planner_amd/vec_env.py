@@ -1699,36 +1699,107 @@ class FFMPVec:
         call; freed by close())."""
         return sum(int(ws.numel()) for ws in (self._nav_ws or {}).values())
 
+    def _nav_plane_obs(self, frames: torch.Tensor) -> "_abi.ObsT":
+        """A copy of the launch struct whose newest frame is the caller's (N, G, G) plane: state_m
+        is the (never read) address one plane before it, the frame stride one plane."""
+        n, G = self.num_envs, self.cfg.grid
+        fmts = {torch.float32: _abi.OBS_F32, torch.uint8: _abi.OBS_U8F16}
+        if not isinstance(frames, torch.Tensor) or tuple(frames.shape) != (n, G, G) or frames.dtype not in fmts \
+                or not frames.is_contiguous() or frames.device != self.device:
+            raise ValueError(f"frames must be a contiguous float32 or uint8 tensor of shape ({n}, {G}, {G}) on {self.device}")
+        ob = _abi.ObsT()
+        C.memmove(C.byref(ob), C.byref(self._obs_c), C.sizeof(ob))
+        ob.state_m = frames.data_ptr() - G * G * frames.element_size()
+        ob.state_m_stride, ob.state_m_frame_stride = G * G, G * G
+        ob.format, ob.reserved = fmts[frames.dtype], 0
+        return ob
+
     def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
-                    cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None) -> None:
+                    cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None,
+                    frames: Optional[torch.Tensor] = None, visible: bool = False) -> None:
         """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
         observation: the newest frame through the window's strides and format, the ego goal from
-        record words 8..9."""
+        record words 8..9.  frames: plan over this (N, G, G) plane instead of the newest frame;
+        visible: over visible_frames(newest_only=True, unknown=0)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError(f"call reset() before {what}()")
+        if visible:
+            if frames is not None:
+                raise ValueError(f"{what}: pass frames or visible=True, not both")
+            frames = self.visible_frames(unknown=0, newest_only=True)
+        obs_c, fmt = self._obs_c, self._fmt
+        if frames is not None:
+            obs_c = self._nav_plane_obs(frames)
+            fmt = obs_c.format
         knobs = (int(margin), int(soft_pen), int(lookahead))
         tile = self._nav_tiled(tile)
         if tile is not None:
-            _abi.check(self.lib.ffmp_nav_field_tiled_check(C.byref(self._cfg_c), self._fmt, *knobs, tile),
+            _abi.check(self.lib.ffmp_nav_field_tiled_check(C.byref(self._cfg_c), fmt, *knobs, tile),
                        "ffmp_nav_field_tiled_check")
             ws = self._nav_workspace(tile, cost is not None)
             with torch.cuda.device(self.device):
-                _abi.check(self.lib.ffmp_nav_field_tiled(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
+                _abi.check(self.lib.ffmp_nav_field_tiled(C.byref(self._cfg_c), self.num_envs, C.byref(obs_c),
                                                          self.record.data_ptr() + 8 * 4, self.record.stride(0), *knobs,
                                                          float(turn_sin), _ptr(cost), _ptr(direction), _ptr(target),
                                                          _ptr(geo_cost), _ptr(cmd), tile, ws.data_ptr(), ws.numel(),
                                                          self._stream()), "ffmp_nav_field_tiled")
             return
-        _abi.check(self.lib.ffmp_nav_field_check(C.byref(self._cfg_c), self._fmt, *knobs), "ffmp_nav_field_check")
+        _abi.check(self.lib.ffmp_nav_field_check(C.byref(self._cfg_c), fmt, *knobs), "ffmp_nav_field_check")
         with torch.cuda.device(self.device):
-            _abi.check(self.lib.ffmp_nav_field(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
+            _abi.check(self.lib.ffmp_nav_field(C.byref(self._cfg_c), self.num_envs, C.byref(obs_c),
                                                self.record.data_ptr() + 8 * 4, self.record.stride(0), *knobs,
                                                float(turn_sin), _ptr(cost), _ptr(direction), _ptr(target),
                                                _ptr(geo_cost), _ptr(cmd), self._stream()), "ffmp_nav_field")
 
+    # ------------------------------------------------ sensor-visible frames (DESIGN §3 a17b, §5.10)
+    def _visible_launch(self, record: torch.Tensor, older: Optional[int], newest: Optional[int], env_stride: int,
+                        fmt: int, unknown: int, max_range: Optional[float], mask=None, flags: int = 0) -> None:
+        """One ffmp_visible_frames launch over `record` (n, R) on the current stream; older / newest
+        are device addresses (None: that frame is not computed)."""
+        mr = float("inf") if max_range is None else float(max_range)
+        _abi.check(self.lib.ffmp_visible_frames_check(C.byref(self._cfg_c), fmt, int(unknown), mr, int(flags)),
+                   "ffmp_visible_frames_check")
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_visible_frames(C.byref(self._cfg_c), record.shape[0], record.data_ptr(),
+                                                    record.stride(0), _ptr(mask), older, newest, int(env_stride), fmt,
+                                                    int(unknown), mr, int(flags), self._stream()), "ffmp_visible_frames")
+
+    def visible_frames(self, out: Optional[torch.Tensor] = None, unknown: int = 128, max_range: Optional[float] = None,
+                       newest_only: bool = False, mask: Optional[torch.Tensor] = None, nocull: bool = False) -> torch.Tensor:
+        """What a sensor at the robot can see of the frame pair, on the device (include/ffmp.h
+        ffmp_visible_frames): state_m with every cell an obstacle disc hides from the ego origin — and
+        every cell farther than `max_range` metres, when given — set to `unknown` (a byte; 0 is the
+        image of a hit-based estimator, where hidden things are simply absent).  (N, 2, G, G)
+        [older, newest], or (N, G, G) with newest_only, in the env's frame dtype (float32, or uint8
+        with obs_format="u8f16").  Computed from `record` on the current stream by one launch, so a
+        caller can capture it into a graph of their own; the step and its frames are untouched.
+        out: write into this contiguous tensor instead of a new one; mask: (N,) bool or uint8, envs
+        with 0 keep their cells of `out`; nocull: the kernel without its culls (the same bits)."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before visible_frames()")
+        n, G = self.num_envs, self.cfg.grid
+        shape = (n, G, G) if newest_only else (n, 2, G, G)
+        if out is None:
+            out = torch.empty(shape, dtype=self._frame_dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != self._frame_dtype or not out.is_contiguous() \
+                or out.device != self.device:
+            raise ValueError(f"out must be a contiguous {self._frame_dtype} tensor of shape {shape} on {self.device}")
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=self.device).reshape(n).to(torch.uint8).contiguous()
+        G2 = G * G
+        if newest_only:
+            older, newest, stride = None, out.data_ptr(), G2
+        else:
+            older, newest, stride = out.data_ptr(), out.data_ptr() + G2 * self._fes, 2 * G2
+        self._visible_launch(self.record, older, newest, stride, self._fmt, unknown, max_range, mask,
+                             _abi.VISIBLE_NOCULL if nocull else 0)
+        return out
+
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
-                  lookahead: int = 4, tile: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                  lookahead: int = 4, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
+                  visible: bool = False) -> Dict[str, torch.Tensor]:
         """The navigation field of the current observation, on the device (include/ffmp.h
         ffmp_nav_field): the cost-to-go from the goal cell over the traversable cells of the newest
         ego frame (hard = the footprint-dilated occupancy; a `margin`-cell zone around it costs
@@ -1745,7 +1816,10 @@ class FFMPVec:
         attribute nav_tile) is given, the plane lives in a workspace on the device and is relaxed in
         tiles of `tile` x `tile` cells (0 = the library's default, 256; else a multiple of 32 in
         [32, 256]) — the same bits either way (include/ffmp.h ffmp_nav_field_tiled).  The workspace
-        is allocated on the first such call and kept until close() (nav_workspace_bytes())."""
+        is allocated on the first such call and kept until close() (nav_workspace_bytes()).
+        frames: plan over this contiguous (N, G, G) float32 or uint8 device tensor instead of the
+        newest frame; visible=True: over visible_frames(newest_only=True, unknown=0), what the robot
+        can see with hidden cells taken as free (the usual free-space assumption)."""
         n, G = self.num_envs, self.cfg.grid
         out = {"target": torch.empty((n, 2), dtype=torch.int32, device=self.device),
                "geo_cost": torch.empty(n, dtype=torch.int32, device=self.device)}
@@ -1755,13 +1829,14 @@ class FFMPVec:
             out["dir"] = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
         self._nav_launch("nav_field", margin, soft_pen, lookahead, self.NAV_DEFAULTS["turn_sin"],
                          cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"],
-                         tile=tile)
+                         tile=tile, frames=frames, visible=visible)
         gc = out["geo_cost"].to(torch.float64)
         out["geo_dist"] = torch.where(gc < 0, torch.full_like(gc, float("inf")), gc * (self.cfg.res / 5.0))
         return out
 
     def policy_nav(self, out: Optional[torch.Tensor] = None, margin: int = 2, soft_pen: int = 40, lookahead: int = 4,
-                   turn_sin: float = 0.25, tile: Optional[int] = None) -> torch.Tensor:
+                   turn_sin: float = 0.25, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
+                   visible: bool = False) -> torch.Tensor:
         """The next (v, w) commands (N, 2) float64 from the navigation field of the current
         observation, on the device (include/ffmp.h ffmp_nav_field's follower): head for the cell
         `lookahead` moves down the cheapest path, turning on the spot while it lies more than
@@ -1769,7 +1844,8 @@ class FFMPVec:
         policy_field); stateless, so on an exactly symmetric scene it can dither between two equal
         routes; obstacle velocities are not looked at.  (0, 0) when the goal is unreachable.  `out`:
         write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one.  `tile`: as
-        for nav_field (grids above 256 x 256 always take the tiled kernel)."""
+        for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`: as
+        for nav_field (plan over a plane of the caller's, or over what the robot can see)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_nav()")
@@ -1779,7 +1855,8 @@ class FFMPVec:
                 or out.device != self.device or out.data_ptr() % 16:
             raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
                              f"({self.num_envs}, 2) on {self.device}")
-        self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out, tile=tile)
+        self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out, tile=tile, frames=frames,
+                         visible=visible)
         return out
 
     # ------------------------------------------------ HIP graph of whole steps

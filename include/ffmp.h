@@ -33,6 +33,10 @@
  *                          (src/train.py:66, src/gym_ffmp/envs/ffmp.py:16)
  *   ffmp_raster         -> external /bev_flow_estimator + /temporal_bev_publisher
  *                          (src/train.py:116-121, make_temporal_maps :474-486)
+ *   ffmp_visible_frames -> what the sensor-driven /bev_flow_estimator can show of those frames
+ *                          (/bev/temporal_bev_image, src/train.py:116-121): nothing an obstacle
+ *                          hides from the robot; the node is outside the reference's repository,
+ *                          so the line-of-sight rule is this header's own [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -511,6 +515,58 @@ int ffmp_nav_field_tiled(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs
 int ffmp_nav_field_tiled_check(const ffmp_cfg_t* cfg, int32_t format, int32_t margin, int32_t soft_pen, int32_t lookahead,
                                int32_t tile);
 int ffmp_nav_field_tiled_workspace(const ffmp_cfg_t* cfg, int64_t n, int32_t tile, int with_cost, size_t* bytes);
+
+/* Sensor-visible occupancy frames (an addition within ABI 9: no existing symbol, struct or value
+ * changes) — stands in for what the reference's external, sensor-driven BEV node shows
+ * (/bev_flow_estimator -> /bev/temporal_bev_image, src/train.py:116-121): an image that cannot
+ * contain what an obstacle hides from the robot.  That node is not in the reference's repository, so
+ * there is no reference counterpart to pin this against [unpinned]; the SPEC below is the definition.
+ * Inputs per env: the raster record (FFMP_REC_HDR + 12K floats) and cfg.  Two frames: the older one
+ * (header words 4..7 and the K previous-frame discs) and the newest one (header words 0..3 and the K
+ * current-frame discs).  The sensor sits at the ego origin.  All arithmetic is float32, every
+ * expression evaluated left to right as written (products first, then the sum; no FMA contraction);
+ * comparisons as written, so a NaN compares false.  Per frame and cell (i, j):
+ *   ex = (float)i * res_f - half_f;  ey = (float)j * res_f - half_f      (the raster's cell coordinates)
+ *   occ = the raster's occupancy of (ex, ey) under this frame's header and discs
+ *         (outside the world, or dx*dx + dy*dy <= r2_k for any disc k)
+ *   b   = ex*ex + ey*ey
+ *   far = b > rr,   rr = max_range * max_range                           (max_range = +inf: never)
+ *   for each disc k = {ox, oy, r2, r} of this frame with r2 > 0:
+ *       dx = ex - ox;  dy = ey - oy;  inside = dx*dx + dy*dy <= r2
+ *       a  = ex*ox + ey*oy
+ *       oo = ox*ox + oy*oy
+ *       q  = oo - r2
+ *       hides_k = !inside && ( q <= 0  ||  ( a > 0 && a < b && oo*b - a*a <= r2*b ) )
+ *   value = (far || any hides_k) ? unknown : (occ ? 255 : 0)
+ * q <= 0: the sensor is inside disc k and everything outside that disc is hidden.  The last test is
+ * "the segment from the sensor to the cell centre passes within r of the disc's centre" without a
+ * division or a square root.  A cell inside a disc is never hidden by that disc: a disc shows whole
+ * unless another disc hides it.  Parked discs (r = 0) hide nothing.  The world's walls hide nothing:
+ * the free world is convex, so what lies beyond a wall is outside the world and stays 255.
+ * Wherever the value is not `unknown` it is the value the raster's frame (state_m) holds for the cell.
+ * A reset record (word 10 = 1) holds the same header and discs twice, so its two frames come out equal.
+ * unknown: a byte, 0..255 (0: the image of a hit-based estimator, hidden things are simply absent).
+ * format: FFMP_OBS_F32 writes (float)value, FFMP_OBS_U8F16 the byte.
+ * record: DEVICE memory, env e's record at record + e * record_stride floats (4-byte loads).
+ * out_older / out_newest: DEVICE memory, either may be NULL (that frame is not computed); element
+ * (e, i, j) at e * out_env_stride + i*G + j elements — a contiguous (N,2,G,G) block is newest =
+ * older + G*G with stride 2 G*G, a (N,G,G) plane has stride G*G, a slot-major window its own.  Each
+ * lane stores 4 cells at once, so the pointers must be 16-byte (F32) or 4-byte (U8F16) aligned and
+ * out_env_stride a multiple of 4 elements; anything else is refused (there is no scalar-store path).
+ * mask: (n) bytes or NULL = all; an env with mask[e] == 0 keeps its output cells (as ffmp_raster_ex).
+ * flags: FFMP_VISIBLE_NOCULL runs every disc for every cell instead of the discs a wave task's box
+ * can be inside of or shadowed by — the same bits, for checking the culls against.
+ * FFMP_E_ARG, with a message and before any HIP call, for: grid outside 8..4096 or not a multiple of
+ * 4; n_obst outside 0..FFMP_MAX_OBST; an unknown format; unknown outside 0..255; max_range NaN or
+ * negative; unknown flag bits; record NULL; record_stride < FFMP_REC_HDR + 12K; both outputs NULL;
+ * out_env_stride < G*G; a misaligned output or stride; n < 0 or too large for one launch.
+ * n == 0: nothing is launched.
+ * ffmp_visible_frames_check: the checks that need no pointer (shape, format, knobs), no launch. */
+#define FFMP_VISIBLE_NOCULL 1
+int ffmp_visible_frames(const ffmp_cfg_t* cfg, int64_t n, const float* record, int64_t record_stride,
+                        const uint8_t* mask, void* out_older, void* out_newest, int64_t out_env_stride,
+                        int32_t format, int32_t unknown, float max_range, int32_t flags, void* stream);
+int ffmp_visible_frames_check(const ffmp_cfg_t* cfg, int32_t format, int32_t unknown, float max_range, int32_t flags);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
