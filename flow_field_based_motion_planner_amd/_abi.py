@@ -147,6 +147,10 @@ _SIGS = {
     "ffmp_visible_frames": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P, _P, _I64, _I32, _I32, C.c_float, _I32,
                                       _P]),
     "ffmp_visible_frames_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, C.c_float, _I32]),
+    # occupancy frames built from the lidar scan (an addition within ABI 9): the inverse sensor model
+    "ffmp_scan_frames": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _P, _P, _P, _I64, _I32, _I32,
+                                   C.c_float, C.c_float, _I32, _P]),
+    "ffmp_scan_frames_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, C.c_float, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),
@@ -258,6 +262,7 @@ RASTER_NARROW = 128  # FFMP_OBS_U8F16: 4 cells per lane instead of 16
 RASTER_TILE16 = 256
 RASTER_MID8 = 512  # FFMP_OBS_U8F16: 8 cells per lane
 VISIBLE_NOCULL = 1  # FFMP_VISIBLE_NOCULL: ffmp_visible_frames without its culls (the same bits)
+SCAN_PLAIN = 1  # FFMP_SCAN_PLAIN: ffmp_scan_frames with the SPEC's bisection for every cell (the same bits)
 
 
 def set_tuning(key: int, value: int) -> int:

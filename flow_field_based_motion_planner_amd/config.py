@@ -71,6 +71,20 @@ def beam_table(n_beams: int) -> np.ndarray:
     return out
 
 
+def sector_table(n_beams: int) -> np.ndarray:
+    """(L, 2) float32 {cos, sin} of the cone boundaries -pi + (m - 1/2)*2pi/L (robot frame), each the
+    float32 rounding of math.cos / math.sin of the float64 angle: sector m, from boundary m to
+    boundary m + 1, is the cone of beam m (include/ffmp.h ffmp_scan_frames)."""
+    out = np.zeros((n_beams, 2), dtype=np.float32)
+    if n_beams:
+        step = 2.0 * math.pi / n_beams
+        for m in range(n_beams):
+            th = -math.pi + (m - 0.5) * step
+            out[m, 0] = math.cos(th)
+            out[m, 1] = math.sin(th)
+    return out
+
+
 @dataclass
 class FFMPConfig:
     grid: int = 100                 # G (MAP_GRID_NUM, ffmp.py:15)

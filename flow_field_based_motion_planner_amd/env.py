@@ -392,6 +392,15 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before visible_frames()")
         return self._vec_env().visible_frames(**kw)[0].cpu().numpy()
 
+    def lidar_frames(self, **kw):
+        """The occupancy frames built from this one env's scan (FFMPVec.lidar_frames, include/ffmp.h
+        ffmp_scan_frames), as a NumPy array: (2, G, G) [older, newest], or (G, G) with
+        newest_only=True; 0 free, 255 a hit, `unknown` (default 128) everything the scan says nothing
+        about.  `out`, `ranges` and `mask` are the batched call's device tensors of one env."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before lidar_frames()")
+        return self._vec_env().lidar_frames(**kw)[0].cpu().numpy()
+
     def render(self, mode="human"):
         return None
 

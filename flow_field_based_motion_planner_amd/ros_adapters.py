@@ -8,6 +8,9 @@ conversions keep the reference's exact semantics:
   laser_callback (:145-150)          ranges_to_scan_data: keep r with `r != inf and r` — NaN
                                      is kept, 0.0 and +inf are dropped — appended to a list
                                      that starts as [None] (:97) and grows across callbacks
+  LaserScan -> the env's lidar row    scan_to_lidar_row: a scan of any field of view and ray count
+                                     resampled onto the env's L-beam circle, the `ranges=` row
+                                     of FFMPVec.lidar_frames (the map built from the scan)
   temporal_bev_image_callback        image_to_map: mono8 image (H, W) -> float32 (1, H, W),
     (:116-121)                       raw 0..255 (kornia.image_to_tensor(keepdim=True).float())
   robot_position_extractor           odometry_to_pose: (x, y, yaw) with yaw from the quaternion
@@ -54,6 +57,57 @@ def ranges_to_scan_data(ranges: Sequence[float], scan_data: Optional[List] = Non
         if r != float("inf") and r:
             out.append(r)
     return out
+
+
+def scan_to_lidar_row(msg_or_ranges, n_beams: int, angle_min: Optional[float] = None,
+                      angle_increment: Optional[float] = None, range_min: float = 0.0,
+                      range_max: float = float("inf")) -> np.ndarray:
+    """A LaserScan (or its bare `ranges`) resampled onto the env's L-beam full circle: (L,) float32 in
+    the lidar's convention, the `ranges=` row FFMPVec.lidar_frames / ffmp_scan_frames take.
+
+    Ray k of the scan points at angle_min + k * angle_increment (taken from the message when not
+    given; a bare sequence defaults to a full circle from -pi).  Env beam l takes the rays whose
+    wrapped angle falls in its cone [-pi + (l - 1/2) 2pi/L, -pi + (l + 1/2) 2pi/L) — the cone
+    ffmp_scan_frames paints with that beam's range — and of several the nearest finite range.
+    Per ray: NaN, a range <= 0 or below range_min is no data (NaN); one above range_max is no return
+    (+inf).  A message's own range_min / range_max narrow the two arguments.  A cone no ray falls
+    into, or with no usable ray, is NaN (no data: the map keeps `unknown` there), so a 270 degree scan
+    leaves the rear cones NaN and an odd ray count needs no care.
+    scan_to_lidar_row(lidar_to_ranges(row, rm), L, -pi, 2 pi / L) gives `row` back except that -inf
+    (the origin inside a disc, published as 0.0) comes back as NaN: both mean no data to the map."""
+    L = int(n_beams)
+    if L < 1:
+        raise ValueError("n_beams must be >= 1")
+    if hasattr(msg_or_ranges, "ranges"):
+        msg = msg_or_ranges
+        vals = np.asarray(msg.ranges, dtype=np.float64).reshape(-1)
+        if angle_min is None:
+            angle_min = float(msg.angle_min)
+        if angle_increment is None:
+            angle_increment = float(msg.angle_increment)
+        range_min = max(float(range_min), float(getattr(msg, "range_min", range_min)))
+        range_max = min(float(range_max), float(getattr(msg, "range_max", range_max)))
+    else:
+        vals = np.asarray(msg_or_ranges, dtype=np.float64).reshape(-1)
+        if angle_min is None:
+            angle_min = -math.pi
+        if angle_increment is None:
+            angle_increment = 2.0 * math.pi / max(len(vals), 1)
+    step = 2.0 * math.pi / L
+    ang = float(angle_min) + np.arange(len(vals), dtype=np.float64) * float(angle_increment)
+    cone = np.floor((ang + math.pi) / step + 0.5).astype(np.int64) % L
+    with np.errstate(invalid="ignore"):
+        dead = np.isnan(vals) | (vals <= 0.0) | (vals < range_min)
+        none = ~dead & (vals > range_max)
+    hit = ~dead & ~none
+    row = np.full(L, np.nan)
+    row[cone[none]] = np.inf
+    best = np.full(L, np.inf)
+    np.minimum.at(best, cone[hit], vals[hit])
+    has = np.zeros(L, dtype=bool)
+    has[cone[hit]] = True
+    row[has] = best[has]
+    return row.astype(np.float32)
 
 
 def image_to_map(img: np.ndarray) -> np.ndarray:

@@ -36,7 +36,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .config import PRESETS, FFMPConfig, beam_table, preset
+from .config import PRESETS, FFMPConfig, beam_table, preset, sector_table
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -1716,11 +1716,12 @@ class FFMPVec:
 
     def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
                     cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None,
-                    frames: Optional[torch.Tensor] = None, visible: bool = False) -> None:
+                    frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False) -> None:
         """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
         observation: the newest frame through the window's strides and format, the ego goal from
         record words 8..9.  frames: plan over this (N, G, G) plane instead of the newest frame;
-        visible: over visible_frames(newest_only=True, unknown=0)."""
+        visible: over visible_frames(newest_only=True, unknown=0); lidar: over
+        lidar_frames(newest_only=True, unknown=0)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError(f"call reset() before {what}()")
@@ -1728,6 +1729,10 @@ class FFMPVec:
             if frames is not None:
                 raise ValueError(f"{what}: pass frames or visible=True, not both")
             frames = self.visible_frames(unknown=0, newest_only=True)
+        if lidar:
+            if frames is not None:
+                raise ValueError(f"{what}: pass one of frames, visible=True and lidar=True")
+            frames = self.lidar_frames(unknown=0, newest_only=True)
         obs_c, fmt = self._obs_c, self._fmt
         if frames is not None:
             obs_c = self._nav_plane_obs(frames)
@@ -1797,9 +1802,86 @@ class FFMPVec:
                              _abi.VISIBLE_NOCULL if nocull else 0)
         return out
 
+    # ------------------------------------------------ frames built from the lidar scan
+    _sector_cache = None  # L -> (L, 2) float32 device tensor (config.sector_table)
+
+    def _sectors(self, L: int) -> torch.Tensor:
+        if self._sector_cache is None:
+            self._sector_cache = {}
+        if L not in self._sector_cache:
+            self._sector_cache[L] = torch.as_tensor(sector_table(L)).to(self.device).contiguous()
+        return self._sector_cache[L]
+
+    def _scan_launch(self, ranges: torch.Tensor, older: Optional[int], newest: Optional[int], env_stride: int, fmt: int,
+                     unknown: int, thickness: float, range_max: float, mask=None, first=None, flags: int = 0) -> None:
+        """One ffmp_scan_frames launch over `ranges` (n, L) float32 on the current stream; older / newest
+        are device addresses (None: that frame is not written)."""
+        L = int(ranges.shape[1])
+        knobs = (fmt, int(unknown), float(thickness), float(range_max), int(flags))
+        _abi.check(self.lib.ffmp_scan_frames_check(C.byref(self._cfg_c), L, *knobs), "ffmp_scan_frames_check")
+        sectors = self._sectors(L)
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_scan_frames(C.byref(self._cfg_c), ranges.shape[0], ranges.data_ptr(), ranges.stride(0), L,
+                                                 sectors.data_ptr(), _ptr(mask), _ptr(first), older, newest, int(env_stride),
+                                                 *knobs, self._stream()), "ffmp_scan_frames")
+
+    def lidar_frames(self, out: Optional[torch.Tensor] = None, unknown: int = 128, thickness: Optional[float] = None,
+                     range_max: Optional[float] = None, newest_only: bool = False, shift: bool = True,
+                     ranges: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                     plain: bool = False) -> torch.Tensor:
+        """The occupancy frames a robot can build from its own scan, on the device (include/ffmp.h
+        ffmp_scan_frames): per cell, the range of the beam whose cone holds the cell decides between
+        free (0, nearer than the hit), occupied (255, within `thickness` metres of the hit; default
+        res) and `unknown` (a byte: behind the hit, beyond `range_max` metres — default
+        cfg.lidar_range — or in a cone without data).  (N, 2, G, G) [older, newest], or (N, G, G)
+        with newest_only, in the env's frame dtype.  One launch on the current stream (the in-place
+        shift adds the comparison that makes its `first` bytes); the step, its frames and its lidar
+        are untouched.
+        ranges: a contiguous (N, L') float32 device tensor in the lidar's convention (+inf no return,
+        -inf / NaN / <= 0 no data) instead of the env's own `lidar`; L' need not be cfg.n_beams.
+        out=None allocates, and both frames are the current scan.  out: write into this contiguous
+        tensor instead.  With out given and shift=True the pair is advanced in place as
+        make_temporal_maps does: older takes what newest held, newest the current scan; an env on
+        the first observation of an episode (record word 10 != 0: it has just reset) gets two equal
+        frames, as state_m does.  shift=False writes the current scan into both frames.
+        mask: (N,) bool or uint8, envs with 0 keep all their cells of `out`; plain: the kernel
+        without its search shortcut (the same bits)."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before lidar_frames()")
+        n, G = self.num_envs, self.cfg.grid
+        if ranges is None:
+            if self.lidar is None:
+                raise ValueError("lidar_frames: the env has n_beams == 0, pass ranges=")
+            ranges = self.lidar
+        elif not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 or ranges.shape[0] != n or ranges.dtype != torch.float32 \
+                or not ranges.is_contiguous() or ranges.device != self.device:
+            raise ValueError(f"ranges must be a contiguous float32 tensor of shape ({n}, L) on {self.device}")
+        shape = (n, G, G) if newest_only else (n, 2, G, G)
+        first = None
+        if out is None:
+            out = torch.empty(shape, dtype=self._frame_dtype, device=self.device)
+        elif tuple(out.shape) != shape or out.dtype != self._frame_dtype or not out.is_contiguous() \
+                or out.device != self.device:
+            raise ValueError(f"out must be a contiguous {self._frame_dtype} tensor of shape {shape} on {self.device}")
+        elif shift and not newest_only:
+            first = self.record[:, 10] != 0  # bool: one byte per env, 0 or 1
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=self.device).reshape(n).to(torch.uint8).contiguous()
+        G2 = G * G
+        if newest_only:
+            older, newest, stride = None, out.data_ptr(), G2
+        else:
+            older, newest, stride = out.data_ptr(), out.data_ptr() + G2 * self._fes, 2 * G2
+        self._scan_launch(ranges, older, newest, stride, self._fmt, unknown,
+                          self.cfg.res if thickness is None else thickness,
+                          self.cfg.lidar_range if range_max is None else range_max, mask, first,
+                          _abi.SCAN_PLAIN if plain else 0)
+        return out
+
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
                   lookahead: int = 4, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
-                  visible: bool = False) -> Dict[str, torch.Tensor]:
+                  visible: bool = False, lidar: bool = False) -> Dict[str, torch.Tensor]:
         """The navigation field of the current observation, on the device (include/ffmp.h
         ffmp_nav_field): the cost-to-go from the goal cell over the traversable cells of the newest
         ego frame (hard = the footprint-dilated occupancy; a `margin`-cell zone around it costs
@@ -1819,7 +1901,9 @@ class FFMPVec:
         is allocated on the first such call and kept until close() (nav_workspace_bytes()).
         frames: plan over this contiguous (N, G, G) float32 or uint8 device tensor instead of the
         newest frame; visible=True: over visible_frames(newest_only=True, unknown=0), what the robot
-        can see with hidden cells taken as free (the usual free-space assumption)."""
+        can see with hidden cells taken as free (the usual free-space assumption); lidar=True: over
+        lidar_frames(newest_only=True, unknown=0), the map made from the scan alone, what a real
+        robot has.  At most one of the three."""
         n, G = self.num_envs, self.cfg.grid
         out = {"target": torch.empty((n, 2), dtype=torch.int32, device=self.device),
                "geo_cost": torch.empty(n, dtype=torch.int32, device=self.device)}
@@ -1829,14 +1913,14 @@ class FFMPVec:
             out["dir"] = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
         self._nav_launch("nav_field", margin, soft_pen, lookahead, self.NAV_DEFAULTS["turn_sin"],
                          cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"],
-                         tile=tile, frames=frames, visible=visible)
+                         tile=tile, frames=frames, visible=visible, lidar=lidar)
         gc = out["geo_cost"].to(torch.float64)
         out["geo_dist"] = torch.where(gc < 0, torch.full_like(gc, float("inf")), gc * (self.cfg.res / 5.0))
         return out
 
     def policy_nav(self, out: Optional[torch.Tensor] = None, margin: int = 2, soft_pen: int = 40, lookahead: int = 4,
                    turn_sin: float = 0.25, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
-                   visible: bool = False) -> torch.Tensor:
+                   visible: bool = False, lidar: bool = False) -> torch.Tensor:
         """The next (v, w) commands (N, 2) float64 from the navigation field of the current
         observation, on the device (include/ffmp.h ffmp_nav_field's follower): head for the cell
         `lookahead` moves down the cheapest path, turning on the spot while it lies more than
@@ -1844,8 +1928,9 @@ class FFMPVec:
         policy_field); stateless, so on an exactly symmetric scene it can dither between two equal
         routes; obstacle velocities are not looked at.  (0, 0) when the goal is unreachable.  `out`:
         write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one.  `tile`: as
-        for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`: as
-        for nav_field (plan over a plane of the caller's, or over what the robot can see)."""
+        for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`, `lidar`:
+        as for nav_field (plan over a plane of the caller's, over what the robot can see, or over the
+        map made from its scan)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_nav()")
@@ -1856,7 +1941,7 @@ class FFMPVec:
             raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
                              f"({self.num_envs}, 2) on {self.device}")
         self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out, tile=tile, frames=frames,
-                         visible=visible)
+                         visible=visible, lidar=lidar)
         return out
 
     # ------------------------------------------------ HIP graph of whole steps

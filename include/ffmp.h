@@ -37,6 +37,9 @@
  *                          (/bev/temporal_bev_image, src/train.py:116-121): nothing an obstacle
  *                          hides from the robot; the node is outside the reference's repository,
  *                          so the line-of-sight rule is this header's own [unpinned]
+ *   ffmp_scan_frames    -> the same image built from the robot's own /scan (the L ranges of the
+ *                          LaserScan, src/train.py:87,145-150) instead of from ground truth: an
+ *                          inverse sensor model, this header's own [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -567,6 +570,69 @@ int ffmp_visible_frames(const ffmp_cfg_t* cfg, int64_t n, const float* record, i
                         const uint8_t* mask, void* out_older, void* out_newest, int64_t out_env_stride,
                         int32_t format, int32_t unknown, float max_range, int32_t flags, void* stream);
 int ffmp_visible_frames_check(const ffmp_cfg_t* cfg, int32_t format, int32_t unknown, float max_range, int32_t flags);
+
+/* Occupancy frames built from the lidar scan (an addition within ABI 9: no existing symbol, struct or
+ * value changes) — the inverse sensor model: the map a robot can make of its own /scan, where
+ * ffmp_visible_frames still reads the ground-truth disc list.  The reference's BEV node builds its
+ * image from sensor data (src/train.py:87,116-121,145-150) but is not in its repository, so there is
+ * no reference counterpart to pin this against [unpinned]; the SPEC below is the definition.
+ * Inputs per env:
+ *   ranges  a row of L float32 ranges in the env's lidar convention: beam l at angle -pi + l*2pi/L in
+ *           the robot frame; +inf = no return, -inf = the origin is inside a disc, NaN = no data.
+ *   u       the sector table (L, 2) float32, supplied by the caller: u[m] is the float32 rounding of
+ *           (cos, sin) of the float64 angle -pi + (m - 1/2)*2pi/L (math.cos / math.sin on the host;
+ *           config.sector_table(L)).  Sector m is the cone of beam m.
+ * All arithmetic is float32, every expression evaluated left to right as written (products first,
+ * then the sum; no FMA contraction); comparisons as written, so a NaN compares false.  Per cell (i, j):
+ *   ex = (float)i * res_f - half_f;  ey = (float)j * res_f - half_f      (the raster's cell coordinates)
+ *   H  = (L + 1) / 2                                                      (integer)
+ *   c0 = u[0].x*ey - u[0].y*ex
+ *   (lo, hi) = c0 >= 0 ? (0, H) : (H - 1, L)
+ *   while hi - lo > 1:  mid = (lo + hi) >> 1;  t = u[mid].x*ey - u[mid].y*ex;  if t >= 0: lo = mid  else: hi = mid
+ *   r  = ranges[lo]
+ *   b  = ex*ex + ey*ey;   mm = range_max_f * range_max_f;   lo_r = r - th;   hi_r = r + th
+ *   known = (b <= mm) && (r > 0)                       (NaN, 0, negative, -inf: no data for this cone)
+ *   free  = (lo_r > 0) && (b < lo_r*lo_r)
+ *   occ   = b <= hi_r*hi_r
+ *   value = !known ? unknown : free ? 0 : occ ? 255 : unknown
+ * The procedure is the definition, not "the nearest beam by atan2": where a cell centre lies exactly
+ * on a cone boundary the two differ, by tens of cells and depending on how the atan2 form breaks
+ * its ties (142 of the 4,096 cell centres lie within 1e-4 rad of a boundary at G = 64, L = 180).
+ * unknown: a byte, 0..255.  thickness (th): the hit's thickness in metres, >= 0 and finite (res gives
+ * an arc two cells thick with no radial holes).  range_max: > 0 or +inf; a +inf range gives free
+ * space out to range_max.  format: FFMP_OBS_F32 writes (float)value, FFMP_OBS_U8F16 the byte.
+ * n_beams: L, 1..FFMP_MAX_BEAMS — an argument, not cfg.n_beams (which is not looked at): a caller may
+ * bring a scan to an env built with L = 0.
+ * ranges: DEVICE memory, env e's row at ranges + e * ranges_stride floats.  sectors: DEVICE memory,
+ * 2L floats.  mask: (n) bytes or NULL = all; an env with mask[e] == 0 keeps all its cells, older included.
+ * The temporal pair (make_temporal_maps, train.py:474-486): first is (n) bytes or NULL.
+ *   out_older given and (first == NULL or first[e] != 0, or out_newest == NULL): older gets the new value too;
+ *   out_older given and first[e] == 0: each cell of older gets the value out_newest held for that cell
+ *       before the call — the lane that reads the cell is the lane that then stores it;
+ *   out_older == NULL: only newest is written.
+ * out_older / out_newest: DEVICE memory, addressed as in ffmp_visible_frames: element (e, i, j) at
+ * e * out_env_stride + i*G + j elements; 16-byte (F32) or 4-byte (U8F16) aligned pointers and a stride
+ * that is a multiple of 4 elements and >= G*G; anything else is refused (there is no scalar-store
+ * path).  No plane of one frame may overlap a plane of the other.
+ * flags: FFMP_SCAN_PLAIN runs the SPEC's bisection for every cell.  Without it a lane's second to
+ * fourth cells start from the previous cell's cone: they look for "t(lo) >= 0 and t(lo + 1) < 0"
+ * inside the cell's own half-turn at that cone and its two neighbours, and bisect only when none of
+ * the three has it — the same bits, the predicate being monotone in m inside a half-turn
+ * (csrc/ffmp_scan.hip).
+ * FFMP_E_ARG, with a message and before any HIP call, for: grid outside 8..4096 or not a multiple of
+ * 4; n_beams outside 1..FFMP_MAX_BEAMS; an unknown format; unknown outside 0..255; thickness NaN,
+ * negative or infinite; range_max NaN or <= 0; unknown flag bits; ranges or sectors NULL;
+ * ranges_stride < n_beams; both outputs NULL; out_env_stride < G*G; a misaligned output or stride;
+ * overlapping older and newest planes (closer than G*G elements, across envs included); n < 0 or too
+ * large for one launch.  n == 0: nothing is launched.
+ * ffmp_scan_frames_check: the checks that need no pointer (shape, format, knobs), no launch. */
+#define FFMP_SCAN_PLAIN 1
+int ffmp_scan_frames(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t ranges_stride, int32_t n_beams,
+                     const float* sectors, const uint8_t* mask, const uint8_t* first,
+                     void* out_older, void* out_newest, int64_t out_env_stride, int32_t format, int32_t unknown,
+                     float thickness, float range_max, int32_t flags, void* stream);
+int ffmp_scan_frames_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t format, int32_t unknown,
+                           float thickness, float range_max, int32_t flags);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
