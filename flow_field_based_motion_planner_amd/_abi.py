@@ -151,6 +151,11 @@ _SIGS = {
     "ffmp_scan_frames": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _P, _P, _P, _I64, _I32, _I32,
                                    C.c_float, C.c_float, _I32, _P]),
     "ffmp_scan_frames_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, C.c_float, _I32]),
+    # the accumulated scan map (an addition within ABI 9): log-odds over time with ego-motion compensation
+    "ffmp_scan_map": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P,
+                                _I64, _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
+    "ffmp_scan_map_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32,
+                                      _I32, _I32, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

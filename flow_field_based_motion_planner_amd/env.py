@@ -401,6 +401,14 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before lidar_frames()")
         return self._vec_env().lidar_frames(**kw)[0].cpu().numpy()
 
+    def lidar_map(self, **kw):
+        """The accumulated scan map of this one env (FFMPVec.lidar_map, include/ffmp.h ffmp_scan_map): the
+        LidarMap holder of the inner batched env — update() it after reset() / step(); its `frame` and
+        `log_odds` are device tensors of shape (1, G, G)."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before lidar_map()")
+        return self._vec_env().lidar_map(**kw)
+
     def render(self, mode="human"):
         return None
 

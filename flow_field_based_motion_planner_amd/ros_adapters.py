@@ -15,6 +15,8 @@ conversions keep the reference's exact semantics:
     (:116-121)                       raw 0..255 (kornia.image_to_tensor(keepdim=True).float())
   robot_position_extractor           odometry_to_pose: (x, y, yaw) with yaw from the quaternion
     (:157-165)                       (tf euler_from_quaternion, axes 'sxyz'), stamp -> seconds
+  Odometry -> the map's pose words    odom_to_pose_row: {x, y, cos yaw, sin yaw} float32, the `pose=`
+                                     row of LidarMap.update (the accumulated scan map)
   pose_array_callback (:126-132)     pose_array_to_start_goal: poses[0], poses[1];
                                      pose_array_to_scenario: that start / goal plus the discs as
                                      the arrays FFMPVec.set_scenarios / FFMP.reset(options=) take
@@ -146,6 +148,19 @@ def odometry_to_pose(msg) -> Tuple[float, float, float, float]:
     st = msg.header.stamp
     t = float(st.to_sec()) if hasattr(st, "to_sec") else float(st.secs) + 1e-9 * float(st.nsecs)
     return float(p.x), float(p.y), quaternion_to_yaw(q.x, q.y, q.z, q.w), t
+
+
+def odom_to_pose_row(msg) -> np.ndarray:
+    """nav_msgs/Odometry -> the four float32 pose words {x, y, cos yaw, sin yaw} of record words 0..3:
+    one row of the `pose=` tensor LidarMap.update / ffmp_scan_map take.  The yaw is quaternion_to_yaw's
+    (which normalises: a non-unit quaternion gives the yaw of its direction, a (near-)zero one yaw 0),
+    cos and sin are math.cos / math.sin of it rounded to float32.  A non-finite position or
+    quaternion gives non-finite words, and the map restarts that env (include/ffmp.h ffmp_scan_map)."""
+    p = msg.pose.pose.position
+    q = msg.pose.pose.orientation
+    quat = (float(q.x), float(q.y), float(q.z), float(q.w))
+    yaw = quaternion_to_yaw(*quat) if all(math.isfinite(v) for v in quat) else float("nan")
+    return np.array([float(p.x), float(p.y), math.cos(yaw), math.sin(yaw)], dtype=np.float32)
 
 
 def pose_array_to_start_goal(msg) -> Tuple[Tuple[float, float], Tuple[float, float]]:

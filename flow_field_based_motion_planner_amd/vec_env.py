@@ -1716,12 +1716,13 @@ class FFMPVec:
 
     def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
                     cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None,
-                    frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False) -> None:
+                    frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False,
+                    lidar_map: Optional["LidarMap"] = None) -> None:
         """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
         observation: the newest frame through the window's strides and format, the ego goal from
         record words 8..9.  frames: plan over this (N, G, G) plane instead of the newest frame;
         visible: over visible_frames(newest_only=True, unknown=0); lidar: over
-        lidar_frames(newest_only=True, unknown=0)."""
+        lidar_frames(newest_only=True, unknown=0); lidar_map: over that LidarMap's frame."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError(f"call reset() before {what}()")
@@ -1733,6 +1734,12 @@ class FFMPVec:
             if frames is not None:
                 raise ValueError(f"{what}: pass one of frames, visible=True and lidar=True")
             frames = self.lidar_frames(unknown=0, newest_only=True)
+        if lidar_map is not None:
+            if frames is not None:
+                raise ValueError(f"{what}: pass one of frames, visible=True, lidar=True and lidar_map")
+            if not isinstance(lidar_map, LidarMap) or lidar_map.env is not self or lidar_map.frame is None:
+                raise ValueError(f"{what}: lidar_map must be a LidarMap of this env that keeps a frame")
+            frames = lidar_map.frame
         obs_c, fmt = self._obs_c, self._fmt
         if frames is not None:
             obs_c = self._nav_plane_obs(frames)
@@ -1879,9 +1886,27 @@ class FFMPVec:
                           _abi.SCAN_PLAIN if plain else 0)
         return out
 
+    # ------------------------------------------------ the accumulated scan map
+    def lidar_map(self, unknown: int = 128, thickness: Optional[float] = None, range_max: Optional[float] = None,
+                  l_hit: int = 8, l_free: int = 4, l_max: int = 64, decay: int = 0, occ_thr: int = 8, free_thr: int = 4,
+                  frame: bool = True) -> "LidarMap":
+        """A map of the scan that remembers (include/ffmp.h ffmp_scan_map): an int8 log-odds plane per
+        env, ego-centric, moved along with the robot and updated from the scan by every
+        LidarMap.update() — a hit adds `l_hit`, a free cell subtracts `l_free`, saturating at
+        +-`l_max`; a cell the scan says nothing about keeps its value, less `decay` toward 0.  The
+        frame holds 255 where the log-odds are >= `occ_thr`, 0 where <= -`free_thr`, else `unknown`.
+        thickness, range_max: as for lidar_frames.  frame=False keeps no frame.  Known limits: a
+        moving obstacle leaves a trail of stale hits until the beam sweeps it free again or `decay`
+        fades it, and the nearest-neighbour re-sampling jitters edges by up to a cell."""
+        self._check_open()
+        return LidarMap(self, unknown, self.cfg.res if thickness is None else thickness,
+                        self.cfg.lidar_range if range_max is None else range_max, l_hit, l_free, l_max, decay, occ_thr,
+                        free_thr, frame)
+
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
                   lookahead: int = 4, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
-                  visible: bool = False, lidar: bool = False) -> Dict[str, torch.Tensor]:
+                  visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None
+                  ) -> Dict[str, torch.Tensor]:
         """The navigation field of the current observation, on the device (include/ffmp.h
         ffmp_nav_field): the cost-to-go from the goal cell over the traversable cells of the newest
         ego frame (hard = the footprint-dilated occupancy; a `margin`-cell zone around it costs
@@ -1903,7 +1928,8 @@ class FFMPVec:
         newest frame; visible=True: over visible_frames(newest_only=True, unknown=0), what the robot
         can see with hidden cells taken as free (the usual free-space assumption); lidar=True: over
         lidar_frames(newest_only=True, unknown=0), the map made from the scan alone, what a real
-        robot has.  At most one of the three."""
+        robot has; lidar_map=m: over m.frame, the accumulated map of a LidarMap of this env (make it
+        with unknown=0 to count unknown cells as free; the caller updates it).  At most one of the four."""
         n, G = self.num_envs, self.cfg.grid
         out = {"target": torch.empty((n, 2), dtype=torch.int32, device=self.device),
                "geo_cost": torch.empty(n, dtype=torch.int32, device=self.device)}
@@ -1913,14 +1939,14 @@ class FFMPVec:
             out["dir"] = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
         self._nav_launch("nav_field", margin, soft_pen, lookahead, self.NAV_DEFAULTS["turn_sin"],
                          cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"],
-                         tile=tile, frames=frames, visible=visible, lidar=lidar)
+                         tile=tile, frames=frames, visible=visible, lidar=lidar, lidar_map=lidar_map)
         gc = out["geo_cost"].to(torch.float64)
         out["geo_dist"] = torch.where(gc < 0, torch.full_like(gc, float("inf")), gc * (self.cfg.res / 5.0))
         return out
 
     def policy_nav(self, out: Optional[torch.Tensor] = None, margin: int = 2, soft_pen: int = 40, lookahead: int = 4,
                    turn_sin: float = 0.25, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
-                   visible: bool = False, lidar: bool = False) -> torch.Tensor:
+                   visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None) -> torch.Tensor:
         """The next (v, w) commands (N, 2) float64 from the navigation field of the current
         observation, on the device (include/ffmp.h ffmp_nav_field's follower): head for the cell
         `lookahead` moves down the cheapest path, turning on the spot while it lies more than
@@ -1928,9 +1954,9 @@ class FFMPVec:
         policy_field); stateless, so on an exactly symmetric scene it can dither between two equal
         routes; obstacle velocities are not looked at.  (0, 0) when the goal is unreachable.  `out`:
         write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one.  `tile`: as
-        for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`, `lidar`:
-        as for nav_field (plan over a plane of the caller's, over what the robot can see, or over the
-        map made from its scan)."""
+        for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`, `lidar`,
+        `lidar_map`: as for nav_field (plan over a plane of the caller's, over what the robot can see,
+        over the map made from its scan, or over the accumulated map)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_nav()")
@@ -1941,7 +1967,7 @@ class FFMPVec:
             raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
                              f"({self.num_envs}, 2) on {self.device}")
         self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out, tile=tile, frames=frames,
-                         visible=visible, lidar=lidar)
+                         visible=visible, lidar=lidar, lidar_map=lidar_map)
         return out
 
     # ------------------------------------------------ HIP graph of whole steps
@@ -2176,6 +2202,115 @@ class FFMPVec:
 
 
 __all__ = ["FFMPVec", "PRESETS"]
+
+
+class LidarMap:
+    """The accumulated scan map of an FFMPVec (FFMPVec.lidar_map; include/ffmp.h ffmp_scan_map, DESIGN §3
+    a19c): two (N, G, G) int8 log-odds planes used as a ping-pong pair, the (N, G, G) frame in the env's
+    frame dtype, and the pose words and episode ids of the last update — the previous pose is the
+    holder's own, so an update after any number of steps uses the right motion, a second update in
+    the same step is an identity warp, and a missed auto-reset is still caught through the episode id.
+    The step, its frames, its lidar and its record are never written."""
+
+    def __init__(self, env: FFMPVec, unknown: int, thickness: float, range_max: float, l_hit: int, l_free: int, l_max: int,
+                 decay: int, occ_thr: int, free_thr: int, frame: bool = True):
+        self.env = env
+        self.knobs = (env._fmt, int(unknown), float(thickness), float(range_max), int(l_hit), int(l_free), int(l_max),
+                      int(decay), int(occ_thr), int(free_thr))
+        _abi.check(env.lib.ffmp_scan_map_check(C.byref(env._cfg_c), 1, *self.knobs, 0), "ffmp_scan_map_check")
+        n, G = env.num_envs, env.cfg.grid
+        self._planes = torch.zeros((2, n, G, G), dtype=torch.int8, device=env.device)
+        self._cur = 0
+        self.frame = torch.full((n, G, G), int(unknown), dtype=env._frame_dtype, device=env.device) if frame else None
+        self._pose = torch.zeros((n, 4), dtype=torch.float32, device=env.device)
+        self._episode = torch.full((n,), -1, dtype=torch.int32, device=env.device)  # no episode: every env restarts
+
+    @property
+    def log_odds(self) -> torch.Tensor:
+        """The current (N, G, G) int8 plane: 0 nothing known, positive occupied, negative free."""
+        return self._planes[self._cur]
+
+    def _mask(self, mask) -> Optional[torch.Tensor]:
+        if mask is None:
+            return None
+        return torch.as_tensor(mask, device=self.env.device).reshape(self.env.num_envs).to(torch.uint8).contiguous()
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Forget the map of the selected envs (mask: (N,) bool or uint8; None = all): log-odds 0, the
+        frame `unknown`, and the next update restarts them."""
+        if mask is None:
+            self.log_odds.zero_()
+            self._episode.fill_(-1)
+            if self.frame is not None:
+                self.frame.fill_(self.knobs[1])
+            return
+        sel = self._mask(mask).bool()
+        self.log_odds[sel] = 0
+        self._episode[sel] = -1
+        if self.frame is not None:
+            self.frame[sel] = self.knobs[1]
+
+    def update(self, ranges: Optional[torch.Tensor] = None, pose: Optional[torch.Tensor] = None,
+               first: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, plain: bool = False
+               ) -> Optional[torch.Tensor]:
+        """Move the map into the current ego frame and add the current scan: one launch on the current
+        stream, then two tiny copies (the pose words and episode ids) on the same stream.  Returns
+        the frame.
+        ranges: a contiguous (N, L') float32 device tensor instead of the env's `lidar`, as in
+        lidar_frames.  pose: a contiguous (N, 4) float32 device tensor {x, y, cos yaw, sin yaw}
+        instead of record words 0..3 (ros_adapters.odom_to_pose_row makes a row).  first: (N,) bool,
+        the envs whose map starts anew; by default the envs whose episode id has changed since the
+        last update or whose record says it has just reset — with pose= given the env's own
+        bookkeeping is not looked at, and without first= no env restarts (but those never updated or
+        reset()).  mask: (N,) bool or uint8, envs with 0 keep their map, their frame and their saved
+        pose.  plain: the kernel without its search shortcut (the same bits)."""
+        env = self.env
+        env._check_open()
+        if env._needs_reset:
+            raise RuntimeError("call reset() before LidarMap.update()")
+        n, G = env.num_envs, env.cfg.grid
+        if ranges is None:
+            if env.lidar is None:
+                raise ValueError("LidarMap.update: the env has n_beams == 0, pass ranges=")
+            ranges = env.lidar
+        elif not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 or ranges.shape[0] != n or ranges.dtype != torch.float32 \
+                or not ranges.is_contiguous() or ranges.device != env.device:
+            raise ValueError(f"ranges must be a contiguous float32 tensor of shape ({n}, L) on {env.device}")
+        never = self._episode < 0
+        if pose is None:
+            pose = env.record
+            if first is None:
+                first = (env.episode != self._episode) | (env.record[:, 10] != 0)
+            episode = env.episode
+        else:
+            if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (n, 4) or pose.dtype != torch.float32 \
+                    or not pose.is_contiguous() or pose.device != env.device:
+                raise ValueError(f"pose must be a contiguous float32 tensor of shape ({n}, 4) on {env.device}")
+            episode = torch.zeros_like(self._episode)
+        if first is None:
+            first = never
+        else:
+            first = torch.as_tensor(first, device=env.device).reshape(n).bool() | never
+        mask = self._mask(mask)
+        L = int(ranges.shape[1])
+        flags = _abi.SCAN_PLAIN if plain else 0
+        _abi.check(env.lib.ffmp_scan_map_check(C.byref(env._cfg_c), L, *self.knobs, flags), "ffmp_scan_map_check")
+        sectors = env._sectors(L)
+        src, dst = self._planes[self._cur], self._planes[1 - self._cur]
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_scan_map(C.byref(env._cfg_c), n, ranges.data_ptr(), ranges.stride(0), L,
+                                             sectors.data_ptr(), pose.data_ptr(), pose.stride(0), self._pose.data_ptr(), 4,
+                                             _ptr(mask), first.data_ptr(), src.data_ptr(), dst.data_ptr(), G * G,
+                                             _ptr(self.frame), G * G, *self.knobs, flags, env._stream()), "ffmp_scan_map")
+        if mask is None:
+            self._pose.copy_(pose[:, 0:4])
+            self._episode.copy_(episode)
+        else:
+            sel = mask.bool()
+            self._pose.copy_(torch.where(sel.unsqueeze(1), pose[:, 0:4], self._pose))
+            self._episode.copy_(torch.where(sel, episode, self._episode))
+        self._cur = 1 - self._cur
+        return self.frame
 
 
 class StepGraph:

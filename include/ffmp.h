@@ -40,6 +40,8 @@
  *   ffmp_scan_frames    -> the same image built from the robot's own /scan (the L ranges of the
  *                          LaserScan, src/train.py:87,145-150) instead of from ground truth: an
  *                          inverse sensor model, this header's own [unpinned]
+ *   ffmp_scan_map       -> that image with a memory: int8 log-odds per cell, moved with the
+ *                          robot's own motion and updated from every scan [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -633,6 +635,66 @@ int ffmp_scan_frames(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int6
                      float thickness, float range_max, int32_t flags, void* stream);
 int ffmp_scan_frames_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t format, int32_t unknown,
                            float thickness, float range_max, int32_t flags);
+
+/* The accumulated scan map (an addition within ABI 9: no existing symbol, struct or value changes) —
+ * log-odds over time with ego-motion compensation: ffmp_scan_frames has no memory, this keeps one.
+ * As ffmp_scan_frames it has no reference counterpart (the BEV node is outside the reference's
+ * repository) [unpinned]; the SPEC below is the definition.
+ * State: one int8 plane per env, M (G x G): the cell's log-odds in integer units — 0 nothing known,
+ * positive occupied, negative free.  The map is ego-centric like every other plane here (row i is
+ * ego x, column j is ego y, the robot at (G/2, G/2)), so it is re-sampled into the new ego frame on
+ * every update.
+ * Ego motion, per env: float64 from eight float32 words, then rounded to float32.
+ *   pose_now = {px1, py1, c1, s1};  pose_prev = {px0, py0, c0, s0}       (the layout of record words 0..3)
+ *   dx = px1 - px0;  dy = py1 - py0
+ *   cr = c0*c1 + s0*s1
+ *   sr = c0*s1 - s0*c1
+ *   tx = (c0*dx + s0*dy) / double(res_f)
+ *   ty = (c0*dy - s0*dx) / double(res_f)
+ * An env restarts (its prior is 0 everywhere) if its `first` byte is non-zero, or if any of the four
+ * rounded values is not finite.
+ * Per cell (i, j): float32, no FMA contraction, operation order as written.
+ *   a = float(i - G/2);  b = float(j - G/2)
+ *   u = (cr*a - sr*b) + tx
+ *   v = (sr*a + cr*b) + ty
+ *   ru = rintf(u);  rv = rintf(v)                                         (rounding half to even)
+ *   inside = ru >= -G/2 && ru <= G/2 - 1, and the same for rv             (float compares: a NaN is outside)
+ *   prior = M_in[(int)ru + G/2][(int)rv + G/2] if inside and the env does not restart, else 0
+ * (a nearest-neighbour gather).  The class of the cell comes from this scan: exactly ffmp_scan_frames'
+ * classification with the same thickness and range_max (that SPEC is unchanged, the bisection included):
+ *   free = known && free;  hit = known && !free && occ;  no information otherwise.
+ * The `unknown` byte plays no part in this step.  Update: int32 arithmetic, stored as int8.
+ *   hit:            M_out = clamp(prior + l_hit, -l_max, l_max)
+ *   free:           M_out = clamp(prior - l_free, -l_max, l_max)
+ *   no information: M_out = prior - sgn(prior) * min(|prior|, decay)
+ * Frame (optional, FFMP_OBS_F32 writes (float)value, FFMP_OBS_U8F16 the byte):
+ *   value = M_out >= occ_thr ? 255 : M_out <= -free_thr ? 0 : unknown
+ * mask: (n) bytes or NULL = all; an env with mask[e] == 0 gets M_out = M_in copied cell for cell, with
+ * no warp, and its frame is not written.  first: (n) bytes, or NULL = no env restarts on that account.
+ * Knobs: 0 <= l_hit, l_free, decay <= 127; 1 <= l_max, occ_thr, free_thr <= 127.  unknown, thickness,
+ * range_max, n_beams, ranges, sectors and FFMP_SCAN_PLAIN (no search shortcut, the same bits) are as
+ * in ffmp_scan_frames.
+ * Known limits: a moving obstacle leaves a trail of stale hits until the beam sweeps it free again or
+ * decay fades it; nearest-neighbour re-sampling on every update jitters edges by up to a cell.
+ * pose_now / pose_prev: DEVICE memory, env e's four words at pose + e * stride floats (stride >= 4).
+ * map_in / map_out: DEVICE memory, cell (e, i, j) at e * map_env_stride + i*G + j bytes; 4-byte
+ * aligned, map_env_stride a multiple of 4 and >= G*G.  They are different buffers, because the gather
+ * reads arbitrary cells: overlapping planes are refused, by the test ffmp_scan_frames applies to its
+ * pair.  frame_out: NULL, or addressed and aligned as ffmp_scan_frames' outputs with frame_env_stride.
+ * FFMP_E_ARG, with a message and before any HIP call, for: everything ffmp_scan_frames_check refuses;
+ * a knob out of range; ranges, sectors, pose_now, pose_prev, map_in or map_out NULL; a stride that is
+ * too small; a misaligned map plane, frame or stride; overlapping map_in and map_out planes; n < 0 or
+ * too large for one launch.  n == 0: nothing is launched.
+ * ffmp_scan_map_check: the checks that need no pointer (shape, format, knobs), no launch. */
+int ffmp_scan_map(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t ranges_stride, int32_t n_beams,
+                  const float* sectors, const float* pose_now, int64_t pose_now_stride, const float* pose_prev,
+                  int64_t pose_prev_stride, const uint8_t* mask, const uint8_t* first, const int8_t* map_in,
+                  int8_t* map_out, int64_t map_env_stride, void* frame_out, int64_t frame_env_stride, int32_t format,
+                  int32_t unknown, float thickness, float range_max, int32_t l_hit, int32_t l_free, int32_t l_max,
+                  int32_t decay, int32_t occ_thr, int32_t free_thr, int32_t flags, void* stream);
+int ffmp_scan_map_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t format, int32_t unknown, float thickness,
+                        float range_max, int32_t l_hit, int32_t l_free, int32_t l_max, int32_t decay, int32_t occ_thr,
+                        int32_t free_thr, int32_t flags);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
