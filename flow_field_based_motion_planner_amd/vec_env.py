@@ -1566,7 +1566,7 @@ class FFMPVec:
     # ONE step (its env kernel + raster, or the one-launch step), captured lazily for each frame-ring
     # position (graph_period() of them), reading the actions from a static device buffer
     # (`action_buffer`; step(env.action_buffer) skips the copy into it).  Bit-identical to the plain
-    # launches (tests/test_gpu_graph.py).
+    # launches (tests/test_gpu_closed_loop.py).
     _graphs = None
 
     def use_graphs(self, on: bool = True) -> None:
@@ -1852,7 +1852,11 @@ class FFMPVec:
         the first observation of an episode (record word 10 != 0: it has just reset) gets two equal
         frames, as state_m does.  shift=False writes the current scan into both frames.
         mask: (N,) bool or uint8, envs with 0 keep all their cells of `out`; plain: the kernel
-        without its search shortcut (the same bits)."""
+        without its search shortcut (the same bits).
+        Inside a graph capture of the caller's: call it once eagerly first — the sector table of a
+        beam count is built on the host and copied to the device at the first call for that count,
+        a host-to-device copy that has no place in a capture; afterwards the call is one launch (two
+        with the shift)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before lidar_frames()")
@@ -1929,7 +1933,10 @@ class FFMPVec:
         can see with hidden cells taken as free (the usual free-space assumption); lidar=True: over
         lidar_frames(newest_only=True, unknown=0), the map made from the scan alone, what a real
         robot has; lidar_map=m: over m.frame, the accumulated map of a LidarMap of this env (make it
-        with unknown=0 to count unknown cells as free; the caller updates it).  At most one of the four."""
+        with unknown=0 to count unknown cells as free; the caller updates it).  At most one of the four.
+        Inside a graph capture of the caller's: call it once eagerly first, with the same tile and
+        cost= (the tiled kernel's workspace is allocated and its kernel set up at the first such
+        call; lidar=True also builds lidar_frames' sector table then)."""
         n, G = self.num_envs, self.cfg.grid
         out = {"target": torch.empty((n, 2), dtype=torch.int32, device=self.device),
                "geo_cost": torch.empty(n, dtype=torch.int32, device=self.device)}
@@ -1956,7 +1963,8 @@ class FFMPVec:
         write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one.  `tile`: as
         for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`, `lidar`,
         `lidar_map`: as for nav_field (plan over a plane of the caller's, over what the robot can see,
-        over the map made from its scan, or over the accumulated map)."""
+        over the map made from its scan, or over the accumulated map).  Inside a graph capture of the
+        caller's: call it once eagerly first, as for nav_field."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_nav()")
@@ -2001,7 +2009,16 @@ class FFMPVec:
         (steps, N, 2) float64 and replay() takes no actions), or commands=True for an open loop whose
         replay(cmds) takes a (steps, N, 2) block.  Command graphs run plain steps: pipelined=True or
         skewed=True raises ValueError (the skewed launch reads ids a step ahead), and their defaults
-        resolve to off."""
+        resolve to off.
+        The graph holds the config (the seed included) by value: after reset(seed=s), seed(s) or a
+        load_state_dict() with another seed its replay() raises RuntimeError and the steps have to be
+        captured again; the same seed, reset(), reset(mask=), raster() and set_scenarios() leave it
+        valid.
+        Warm-up: a capture runs nothing and copies nothing from the host, so whatever a callable
+        policy calls must have run once before — lidar_frames() builds its sector table on the host
+        at its first call for a beam count, and the tiled nav_field() / policy_nav() allocates its
+        workspace and sets its kernel up at its first call (policy="nav" does that here, before the
+        capture begins).  Call the policy once eagerly, then capture."""
         return StepGraph(self, steps, pipelined, skewed, policy, commands)
 
     # ------------------------------------------------ gym.vector.VectorEnv surface
@@ -2072,11 +2089,18 @@ class FFMPVec:
         """gym 0.17-style: the seed of the next full reset()."""
         self._set_cfg(self.cfg.replace(seed=int(seed)))
 
+    _cfg_gen = 0  # config generation: counts the configs that differed from their predecessor
+
     def _set_cfg(self, cfg: FFMPConfig) -> None:
-        """A new config after construction (a new seed): the launch struct is rebuilt, and the
-        single-step graphs, which captured the old one by value, are dropped (re-captured on use)."""
+        """A new config after construction (a new seed): the launch struct is rebuilt and the
+        config generation moves on.  Graphs captured the old struct by value: the single-step
+        graphs are dropped (re-captured on use), a StepGraph of an older generation refuses to
+        replay.  A config equal to the current one (reset(seed=<the same seed>)) changes nothing."""
+        if cfg == self.cfg:
+            return
         self.cfg = cfg
         self._cfg_c = _abi.make_cfg(self.cfg, _ptr(self.beam_cs) or 0)
+        self._cfg_gen += 1
         if self._graphs is not None:
             self._graphs = {}
 
@@ -2327,6 +2351,15 @@ class StepGraph:
     per-step host work), and the env must not be stepped or reset between capture and replay except
     through whole replays or whole periods of step() calls (checked: the frame position).
 
+    The graph holds the env's config struct (the seed that keys the auto-reset RNG included) by
+    value.  A config change after the capture — reset(seed=s), seed(s) or load_state_dict() of a
+    checkpoint with another seed — makes replay() raise RuntimeError: capture again (it is not done
+    silently).  What does not change the config leaves the graph valid: reset(), reset(seed=<the
+    same seed>), reset(mask=), set_scenarios(), raster(), invalidate_frame_tags(), a load_state_dict()
+    with the same seed (all at the capture's frame position), and launch shapes or tuning changed
+    later (the captured launches keep theirs; the results are the same bits).
+    (tests/test_gpu_graph_state.py.)
+
     Pipelined (two-launch steps, an even step count): the raster of step i reads only the record
     its env kernel wrote, and the env kernel reads none of the raster's outputs, so with two record
     buffers — step i's env kernel writes buffer (i + 1) % 2, the current record being buffer 0 —
@@ -2419,6 +2452,7 @@ class StepGraph:
         self.skewed = bool(skewed)
         snap = (env._wpos, list(env._hist), env._hist_from_reset)
         self.wpos = env._wpos
+        self.cfg_gen = env._cfg_gen  # the launches below hold this generation's config struct by value
         self.graph = torch.cuda.CUDAGraph()
         stream = torch.cuda.Stream(device=env.device)
         if policy == "nav" and env._nav_tiled(None) is not None:
@@ -2520,6 +2554,10 @@ class StepGraph:
         env._check_open()
         if env._needs_reset:
             raise RuntimeError("call reset() before replay()")
+        if env._cfg_gen != self.cfg_gen:
+            raise RuntimeError("the env's config changed since capture (a new seed through reset(seed=), seed() or "
+                               "load_state_dict()): the graph holds the old one and has to be captured again "
+                               "(env.capture())")
         if env._wpos != self.wpos:
             raise RuntimeError("the env's frame position moved since capture (step() a whole graph_period())")
         if actions is not None:
