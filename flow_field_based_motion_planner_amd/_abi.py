@@ -156,6 +156,10 @@ _SIGS = {
                                 _I64, _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "ffmp_scan_map_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32,
                                       _I32, _I32, _I32]),
+    # motion flow estimated from two scan frames (an addition within ABI 9): block matching, ego-motion compensated
+    "ffmp_scan_flow": (C.c_int, [C.POINTER(CfgT), _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32,
+                                 C.c_float, _I32, _I32, _I32, _I32, _P]),
+    "ffmp_scan_flow_check": (C.c_int, [C.POINTER(CfgT), _I32, C.c_float, _I32, _I32, _I32, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

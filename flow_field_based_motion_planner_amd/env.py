@@ -409,6 +409,14 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before lidar_map()")
         return self._vec_env().lidar_map(**kw)
 
+    def lidar_flow(self, **kw):
+        """The motion flow estimated from this one env's scan (FFMPVec.lidar_flow, include/ffmp.h
+        ffmp_scan_flow): the LidarFlow holder of the inner batched env — update() it after reset() /
+        step(); its `flow` (1, 2, G, G) and `kind` (1, G, G) are device tensors."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before lidar_flow()")
+        return self._vec_env().lidar_flow(**kw)
+
     def render(self, mode="human"):
         return None
 

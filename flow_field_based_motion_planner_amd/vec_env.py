@@ -1907,6 +1907,25 @@ class FFMPVec:
                         self.cfg.lidar_range if range_max is None else range_max, l_hit, l_free, l_max, decay, occ_thr,
                         free_thr, frame)
 
+    # ------------------------------------------------ motion flow estimated from the scan
+    def lidar_flow(self, lag: int = 4, radius: int = 4, block: int = 3, gate: int = 1, min_hits: int = 3,
+                   thickness: Optional[float] = None, range_max: Optional[float] = None, kind: bool = True) -> "LidarFlow":
+        """The motion flow a robot can estimate from its own scan (include/ffmp.h ffmp_scan_flow): the
+        sensor-side counterpart of obs["flow"].  Every LidarFlow.update() builds the scan frame, moves
+        the frame of `lag` updates ago into the current ego frame and matches the
+        (2*block+1) x (2*block+1) block of hits around every hit cell against it, over displacements
+        of up to `radius` cells: (N, 2, G, G) [vx, vy] in the env's flow dtype, world velocity in the
+        current ego axes in m/s, a multiple of res / (lag * dt).  A block within `gate` unmatched
+        cells of the warped earlier frame is static (flow 0); one with fewer than `min_hits` hits is
+        not estimated.  thickness, range_max: as for lidar_frames.  kind=False keeps no kind plane
+        (0 no estimate, 1 static, 2 moving).  Known limits: integer displacements of a
+        two-cell-thick arc — one quantum is res / (lag * dt); a straight wall shows no motion along
+        itself (the aperture problem; the gate hides most of it); a disc that reflects off a wall
+        inside the lag gets the net displacement; an env in its first `lag` updates has no flow."""
+        self._check_open()
+        return LidarFlow(self, lag, radius, block, gate, min_hits, self.cfg.res if thickness is None else thickness,
+                         self.cfg.lidar_range if range_max is None else range_max, kind)
+
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
                   lookahead: int = 4, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
                   visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None
@@ -2335,6 +2354,157 @@ class LidarMap:
             self._episode.copy_(torch.where(sel, episode, self._episode))
         self._cur = 1 - self._cur
         return self.frame
+
+
+class LidarFlow:
+    """The motion flow estimated from the scan of an FFMPVec (FFMPVec.lidar_flow; include/ffmp.h
+    ffmp_scan_flow): a ring of lag + 1 uint8 scan frames (lag + 1, N, G, G) — uint8
+    whatever the env's obs_format — with the pose words and the episode id saved beside every frame
+    (-1: the env has no frame in that slot), `updates` (N,) int32, the updates of every env since
+    its restart, and the outputs: `flow` (N, 2, G, G) [vx, vy] in the env's flow dtype and `kind`
+    (N, G, G) uint8 (0 no estimate, 1 static, 2 moving) or None.  An env restarts — flow 0 and kind 0
+    until it has `lag` earlier frames again — when its episode id differs from the one saved at
+    the last update, when its record says it has just reset, or when the last update left it out
+    (mask=): the ring advances for all envs at once, so an env that skips an update loses its
+    history.  The step, its frames, its lidar and its record are never written."""
+
+    MAX_LAG = 16
+
+    def __init__(self, env: FFMPVec, lag: int, radius: int, block: int, gate: int, min_hits: int, thickness: float,
+                 range_max: float, kind: bool = True):
+        lag = int(lag)
+        if not 1 <= lag <= self.MAX_LAG:
+            raise ValueError(f"lag must be in [1, {self.MAX_LAG}], got {lag}")
+        self.env, self.lag = env, lag
+        self.scale = float(np.float32(env.cfg.res / (lag * env.cfg.dt)))
+        self.knobs = (env._fmt, self.scale, int(radius), int(block), int(gate), int(min_hits))
+        self.scan_knobs = (128, float(thickness), float(range_max))
+        _abi.check(env.lib.ffmp_scan_flow_check(C.byref(env._cfg_c), *self.knobs), "ffmp_scan_flow_check")
+        _abi.check(env.lib.ffmp_scan_frames_check(C.byref(env._cfg_c), 1, _abi.OBS_U8F16, *self.scan_knobs, 0),
+                   "ffmp_scan_frames_check")
+        n, G, dev = env.num_envs, env.cfg.grid, env.device
+        self._frames = torch.zeros((lag + 1, n, G, G), dtype=torch.uint8, device=dev)
+        self._poses = torch.zeros((lag + 1, n, 4), dtype=torch.float32, device=dev)
+        self._episodes = torch.full((lag + 1, n), -1, dtype=torch.int32, device=dev)
+        self._pos = 0
+        self.updates = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.flow = torch.zeros((n, 2, G, G), dtype=env._pot_dtype, device=dev)
+        self.kind = torch.zeros((n, G, G), dtype=torch.uint8, device=dev) if kind else None
+
+    @property
+    def frame(self) -> torch.Tensor:
+        """The newest (N, G, G) uint8 scan frame of the ring (lidar_frames(newest_only=True)'s bytes)."""
+        return self._frames[self._pos]
+
+    def _mask(self, mask) -> Optional[torch.Tensor]:
+        if mask is None:
+            return None
+        return torch.as_tensor(mask, device=self.env.device).reshape(self.env.num_envs).to(torch.uint8).contiguous()
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Forget the frames of the selected envs (mask: (N,) bool or uint8; None = all): flow 0, kind 0,
+        and the next update restarts them."""
+        if mask is None:
+            self._episodes.fill_(-1)
+            self.updates.zero_()
+            self.flow.zero_()
+            if self.kind is not None:
+                self.kind.zero_()
+            return
+        sel = self._mask(mask).bool()
+        self._episodes[:, sel] = -1
+        self.updates[sel] = 0
+        self.flow[sel] = 0
+        if self.kind is not None:
+            self.kind[sel] = 0
+
+    def update(self, ranges: Optional[torch.Tensor] = None, pose: Optional[torch.Tensor] = None,
+               first: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Build the current scan frame into the next ring slot and estimate the flow against the frame
+        of `lag` updates ago: two launches on the current stream (ffmp_scan_frames, ffmp_scan_flow) and
+        the small bookkeeping copies on the same stream.  Returns `flow`.
+        ranges: a contiguous (N, L') float32 device tensor instead of the env's `lidar`, as in
+        lidar_frames.  pose: a contiguous (N, 4) float32 device tensor {x, y, cos yaw, sin yaw}
+        instead of record words 0..3 (ros_adapters.odom_to_pose_row makes a row).  first: (N,) bool,
+        the envs that start anew; by default the envs whose episode id has changed since the last
+        update or whose record says it has just reset — with pose= given the env's own bookkeeping
+        is not looked at, and without first= no env restarts (but those never updated, left out of
+        the last update or reset()).  mask: (N,) bool or uint8, envs with 0 keep their flow and kind,
+        and lose their history."""
+        env = self.env
+        env._check_open()
+        if env._needs_reset:
+            raise RuntimeError("call reset() before LidarFlow.update()")
+        n, G, lag = env.num_envs, env.cfg.grid, self.lag
+        if ranges is None:
+            if env.lidar is None:
+                raise ValueError("LidarFlow.update: the env has n_beams == 0, pass ranges=")
+            ranges = env.lidar
+        elif not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 or ranges.shape[0] != n or ranges.dtype != torch.float32 \
+                or not ranges.is_contiguous() or ranges.device != env.device:
+            raise ValueError(f"ranges must be a contiguous float32 tensor of shape ({n}, L) on {env.device}")
+        last = self._episodes[self._pos]
+        if pose is None:
+            pose = env.record
+            episode = env.episode
+            if first is None:
+                first = (episode != last) | (env.record[:, 10] != 0)
+        else:
+            if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (n, 4) or pose.dtype != torch.float32 \
+                    or not pose.is_contiguous() or pose.device != env.device:
+                raise ValueError(f"pose must be a contiguous float32 tensor of shape ({n}, 4) on {env.device}")
+            episode = torch.zeros_like(last)
+        never = last < 0
+        restart = never if first is None else torch.as_tensor(first, device=env.device).reshape(n).bool() | never
+        mask = self._mask(mask)
+        sel = None if mask is None else mask.bool()
+        if sel is not None:
+            restart = restart & sel
+        self._episodes.masked_fill_(restart.unsqueeze(0), -1)
+        slot = (self._pos + 1) % (lag + 1)
+        old = (slot + 1) % (lag + 1)  # the slot of `lag` updates ago
+        G2 = G * G
+        env._scan_launch(ranges, None, self._frames[slot].data_ptr(), G2, _abi.OBS_U8F16, *self.scan_knobs, mask)
+        self._episodes[slot] = episode if sel is None else torch.where(sel, episode, torch.full_like(episode, -1))
+        kfirst = self._episodes[old] != self._episodes[slot]  # bool: one byte per env
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_scan_flow(C.byref(env._cfg_c), n, self._frames[slot].data_ptr(), self._frames[old].data_ptr(),
+                                              G2, pose.data_ptr(), pose.stride(0), self._poses[old].data_ptr(), 4, _ptr(mask),
+                                              kfirst.data_ptr(), self.flow.data_ptr(), 2 * G2, _ptr(self.kind), G2,
+                                              *self.knobs, env._stream()), "ffmp_scan_flow")
+        self._poses[slot] = pose[:, 0:4]
+        one = torch.ones_like(self.updates)
+        nxt = torch.where(restart, one, self.updates + 1)
+        self.updates.copy_(nxt if sel is None else torch.where(sel, nxt, self.updates))
+        self._pos = slot
+        return self.flow
+
+    def bev_image(self, occ: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 4-channel [occupancy, R, G, B] image (include/ffmp.h ffmp_bev_image) with the estimated
+        flow in place of obs["flow"]: (N, 4, G, G) in the env's frame dtype, vmax = cfg.obst_vmax —
+        the reference's 12-channel input from sensor data alone, a ring of these images going
+        through temporal_maps as the ground-truth ones do.  occ: a contiguous (N, G, G) device tensor
+        in the env's frame dtype; by default the newest scan frame of the ring.  out: write into
+        this contiguous tensor instead of a new one."""
+        env = self.env
+        env._check_open()
+        n, G = env.num_envs, env.cfg.grid
+        G2 = G * G
+        if occ is None:
+            occ = self.frame if env._frame_dtype == torch.uint8 else self.frame.to(env._frame_dtype)
+        elif not isinstance(occ, torch.Tensor) or tuple(occ.shape) != (n, G, G) or occ.dtype != env._frame_dtype \
+                or not occ.is_contiguous() or occ.device != env.device:
+            raise ValueError(f"occ must be a contiguous {env._frame_dtype} tensor of shape ({n}, {G}, {G}) on {env.device}")
+        shape = (n, 4, G, G)
+        if out is None:
+            out = torch.empty(shape, dtype=env._frame_dtype, device=env.device)
+        elif tuple(out.shape) != shape or out.dtype != env._frame_dtype or not out.is_contiguous() or out.device != env.device:
+            raise ValueError(f"out must be a contiguous {env._frame_dtype} tensor of shape {shape} on {env.device}")
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_bev_image(n, 1 if env.obs_format == "u8f16" else 0, occ.data_ptr(), G2, self.flow.data_ptr(), G2,
+                                              float(np.float32(env.cfg.obst_vmax)), out.data_ptr(), 4 * G2, env._stream()),
+                       "ffmp_bev_image")
+        return out
 
 
 class StepGraph:

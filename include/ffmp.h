@@ -42,6 +42,9 @@
  *                          inverse sensor model, this header's own [unpinned]
  *   ffmp_scan_map       -> that image with a memory: int8 log-odds per cell, moved with the
  *                          robot's own motion and updated from every scan [unpinned]
+ *   ffmp_scan_flow      -> the flow half of that image (the RGB of "occupancy(MONO) + flow(RGB)",
+ *                          src/gym_ffmp/envs/ffmp.py:16) from two scan frames and the two poses: a
+ *                          per-cell velocity by block matching with ego-motion compensation [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -695,6 +698,63 @@ int ffmp_scan_map(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t
 int ffmp_scan_map_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t format, int32_t unknown, float thickness,
                         float range_max, int32_t l_hit, int32_t l_free, int32_t l_max, int32_t decay, int32_t occ_thr,
                         int32_t free_thr, int32_t flags);
+
+/* Motion flow estimated from the scan (an addition within ABI 9: no existing symbol, struct or value
+ * changes): the sensor-side counterpart of the flow planes of cfg.flow.  Two scan frames `lag` updates
+ * apart and the two poses give a per-cell velocity in the current ego axes, in the layout and units of
+ * obs.flow.  As ffmp_scan_frames it has no reference counterpart (the BEV node is outside the
+ * reference's repository) [unpinned]; the SPEC below is the definition.  Integer arithmetic apart from
+ * the warp and one float multiply.
+ * SPEC, per env.
+ * Motion: (cr, sr, tx, ty), the restart rule and the per-cell (ru, rv, inside) are exactly
+ * ffmp_scan_map's: float64 from eight float32 words, rounded to float32, then float32 left to right,
+ * rintf.
+ * Hit planes: a cell index outside 0..G-1 reads 0 in every plane.
+ *   Hc[i][j]   = cur[i][j] == 255
+ *   Hp[i][j]   = inside && prev[(int)ru + G/2][(int)rv + G/2] == 255
+ *   D(X)[i][j] = OR of X over the 3 x 3 neighbourhood of (i, j)
+ * Restart: if the env restarts (first[e] != 0 or a non-finite motion value), every cell gets kind 0
+ * and flow 0.
+ * Cell with !Hc[i][j]: kind 0, flow 0.
+ * Cell with Hc[i][j]: the block is a, b in -B..B.
+ *   1. nc = sum Hc[i+a][j+b].  If nc < min_hits: kind 0.
+ *   2. c0 = sum (Hc & !D(Hp))[i+a][j+b] + sum (Hp & !D(Hc))[i+a][j+b].  If c0 <= gate: kind 1,
+ *      (du, dv) = (0, 0) — the cell is static within a cell of warp jitter.
+ *   3. Otherwise search.  Visit the displacements |du|, |dv| <= R in ascending order of the key
+ *      (du*du + dv*dv, du, dv).
+ *        np_d = sum Hp[i+a-du][j+b-dv]
+ *        cost = sum Hc[i+a][j+b] ^ Hp[i+a-du][j+b-dv]
+ *      A displacement with np_d < min_hits is skipped.  The first displacement with a strictly smaller
+ *      cost wins.  If none qualifies: kind 0.  Otherwise kind 2.
+ * Flow:
+ *   vx = (float)du * scale;  vy = (float)dv * scale
+ * — one float32 multiply, converted to binary16 round-to-nearest-even under the compact format; the
+ * value is 0.0 for kind 0 and kind 1.  The cell now at i was at i - du, so the sign is that of
+ * obs.flow: world velocity in the current ego axes.  (A caller passes scale = res / (lag * dt).)
+ * Mask: an env with mask[e] == 0 keeps all its cells of both outputs.
+ * Known limits: one quantum is `scale`; a straight wall gives no motion along itself (the aperture
+ * problem: the gate hides most of it); a disc that reflects off a wall between the two frames.
+ * cfg: only grid and res are read.  cur / prev: DEVICE uint8 planes, env e at e * frame_env_stride
+ * bytes, row i ego x, column j ego y — scan frames as ffmp_scan_frames writes them in FFMP_OBS_U8F16;
+ * only == 255 (a hit) is looked at.  pose_now / pose_prev with their strides, mask, first: as in
+ * ffmp_scan_map.  flow_out: (n, 2, G, G), env e at e * flow_env_stride elements, planes vx then vy;
+ * format FFMP_OBS_F32: float32, FFMP_OBS_U8F16: binary16 (obs.flow under the compact layout).
+ * kind_out: uint8 (n, G, G), env e at e * kind_env_stride bytes, or NULL.  Knobs: radius R 1..5,
+ * block B 1..3, gate 0..98, min_hits 1..49.
+ * FFMP_E_ARG, with a message and before any HIP call, for: a grid outside 8..512 or not a multiple of
+ * 4; an unknown format; a knob out of range; scale not finite; cur, prev, pose_now, pose_prev or
+ * flow_out NULL; a stride that is too small (frames and kinds G*G, flow 2*G*G, poses 4); misaligned
+ * planes or strides (frames and kinds 4 bytes, float32 flow 16 bytes, binary16 flow 8 bytes, strides
+ * multiples of 4 elements); overlapping flow_out and kind_out planes, or an output that overlaps the
+ * frames; n < 0 or too large for one launch.  n == 0: nothing is launched.
+ * ffmp_scan_flow_check: the checks that need no pointer (shape, format, knobs), no launch. */
+int ffmp_scan_flow(const ffmp_cfg_t* cfg, int64_t n, const uint8_t* cur, const uint8_t* prev, int64_t frame_env_stride,
+                   const float* pose_now, int64_t pose_now_stride, const float* pose_prev, int64_t pose_prev_stride,
+                   const uint8_t* mask, const uint8_t* first, void* flow_out, int64_t flow_env_stride, uint8_t* kind_out,
+                   int64_t kind_env_stride, int32_t format, float scale, int32_t radius, int32_t block, int32_t gate,
+                   int32_t min_hits, void* stream);
+int ffmp_scan_flow_check(const ffmp_cfg_t* cfg, int32_t format, float scale, int32_t radius, int32_t block, int32_t gate,
+                         int32_t min_hits);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
