@@ -187,6 +187,27 @@ __device__ uint64_t g_trace_ras[65536 * 4];
 
 // One env's raster record: header, goal, then K float4 of each of cur / prev / vel.
 // Lane k writes obstacle k; lanes 0..3 the header words.
+// Word i (0 .. FFMP_REC_HDR - 1) of the header, for a lane-dependent i.  Selects over values read
+// first: a select between the structs' fields (or an array indexed by the lane) becomes a load from
+// a selected stack address, which stays in scratch wherever the register budget is too small for the
+// compiler to turn the stack object into a vector (the one-launch step at a forced occupancy kept
+// 96 B per lane for it, +0.7 % of HBM traffic at C3; the plain one 4 KB of LDS per block).
+FFMP_DEV float record_hdr_word(int i, const FrameHdr& hc, const FrameHdr& hp, float2 ge, float first) {
+  const float c0 = hc.px, c1 = hc.py, c2 = hc.c, c3 = hc.s, p0 = hp.px, p1 = hp.py, p2 = hp.c, p3 = hp.s;
+  float v = 0.0f;
+  v = i == 0 ? c0 : v;
+  v = i == 1 ? c1 : v;
+  v = i == 2 ? c2 : v;
+  v = i == 3 ? c3 : v;
+  v = i == 4 ? p0 : v;
+  v = i == 5 ? p1 : v;
+  v = i == 6 ? p2 : v;
+  v = i == 7 ? p3 : v;
+  v = i == 8 ? ge.x : v;
+  v = i == 9 ? ge.y : v;
+  v = i == 10 ? first : v;
+  return v;
+}
 FFMP_DEV void write_record_hdr(float* rec, int lane, const FrameHdr& hc, const FrameHdr& hp, float2 ge, float first) {
   if (lane == 0) {
     rec[8] = ge.x;
@@ -195,8 +216,8 @@ FFMP_DEV void write_record_hdr(float* rec, int lane, const FrameHdr& hc, const F
     rec[11] = 0.0f;
   }
   if (lane < 4) {
-    rec[lane] = lane == 0 ? hc.px : lane == 1 ? hc.py : lane == 2 ? hc.c : hc.s;
-    rec[4 + lane] = lane == 0 ? hp.px : lane == 1 ? hp.py : lane == 2 ? hp.c : hp.s;
+    rec[lane] = record_hdr_word(lane, hc, hp, ge, first);
+    rec[4 + lane] = record_hdr_word(4 + lane, hc, hp, ge, first);
     rec[12 + lane] = 0.0f;
   }
 }
@@ -431,11 +452,7 @@ FFMP_DEV __attribute__((always_inline)) void env_group(const ffmp_cfg_t& cfg, in
       st.obst_r[e * K + k] = my[j].r;
     }
     if (s_rhdr) {  // the one-launch step: the record's header for the block's raster, in LDS
-      if (lane < FFMP_REC_HDR) {
-        const float hv[FFMP_REC_HDR] = {hcur.px, hcur.py, hcur.c, hcur.s, hprev.px, hprev.py, hprev.c, hprev.s,
-                                        ge.x,    ge.y,    first ? 1.0f : 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        s_rhdr[lane] = hv[lane];
-      }
+      if (lane < FFMP_REC_HDR) s_rhdr[lane] = record_hdr_word(lane, hcur, hprev, ge, first ? 1.0f : 0.0f);
     }
     if (lane == 0) {
       st.pose[e * 3 + 0] = x1; st.pose[e * 3 + 1] = y1; st.pose[e * 3 + 2] = yaw1;
@@ -832,6 +849,20 @@ struct TagArgs {
 struct TagLds {
   uint8_t older[kTagLdsCap], newest[kTagLdsCap];
 };
+// FFMP_RASTER_WAVES: the tagged float32 kernels held to kRasterWaves waves per SIMD
+// (__launch_bounds__(256, W)).  The W rides on the tag argument's type, so the instantiations
+// without it keep their names.  Once the tags took most of the frame stores away the one-launch step
+// was no longer bound by its stores (5.5 of 8 TB/s): half of its wave cycles are parked, and with 113
+// VGPRs only four waves per SIMD cover each other.  At 6 the kernels take 76 VGPRs and no scratch.
+// Asking for 5 compiles to the same 76-77 VGPRs and 6 waves, 7 keeps 12 B per lane of scratch in the
+// one-launch step for the same time, 8 spills in the band loop (profiles/fused_waves_variants.json).
+constexpr int kRasterWaves = 6;
+template <int W>
+struct TagArgsW : TagArgs {};
+template <class... TG>
+constexpr int kTagWaves = 0;
+template <int W>
+constexpr int kTagWaves<TagArgsW<W>> = W;
 struct TagCtx {
   uint8_t* t0;        // this env's tags, older slot
   uint8_t* t1;        // ... newest slot
@@ -869,7 +900,8 @@ FFMP_DEV TagCtx stage_tags(const TagArgs& ta, int64_t e, int qbeg, int qend, int
 // frames and pot binary16 planes (the pointers are reinterpreted; strides in elements).
 // PRELOADED: the record is already in the block's LDS (s_hdr, s_cur, s_prev, s_vel; written by the
 // one-launch step's env_group before a block barrier), so the raster does not read it back from HBM.
-template <bool NT, bool FLOW, int FMT, bool PRELOADED = false, bool TAGS = false>
+// WV > 0: the kernel is held to WV waves per SIMD (FFMP_RASTER_WAVES; tagged float32 frames without flow planes).
+template <bool NT, bool FLOW, int FMT, bool PRELOADED = false, bool TAGS = false, int WV = 0>
 FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, int64_t e, int tile, int32_t cells_per_block,
                                                         const float* __restrict__ record,
                                                         float* __restrict__ state_m, int64_t sm_stride,
@@ -879,6 +911,7 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
                                                         float2* s_vel, float* s_hdr, const TagCtx& tagc = TagCtx{}) {
   constexpr bool CT = FMT != FMT_F32;
   static_assert(!TAGS || FMT == FMT_F32, "granule tags: float32 frames only");
+  static_assert(WV == 0 || (TAGS && !FLOW), "forced occupancy: tagged float32 frames without flow planes");
   constexpr int CPL = FMT == FMT_CT16 ? 16 : FMT == FMT_CT8 ? 8 : 4;  // cells per lane in a wave task
   constexpr int WC = 64 * CPL;                   // cells per wave task
   const int K = cfg.n_obst;
@@ -905,7 +938,8 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
   // 11 VGPRs — 108 -> 72 VGPRs, 4 -> 7 waves per SIMD, compact C3 raster 1.15-1.29 -> 1.00-1.13 ms
   // (profiles/r02_occupancy.txt).  Not for the float32 layout (store-bound: 7 waves per SIMD ran
   // its steps ~2 % slower than 4) nor for FMT_CT16 (the scheduler then took 188 VGPRs, not 167).
-  auto hv = [&](int i) { return (FMT == FMT_CT4 || FMT == FMT_CT8) ? uni(s_hdr[i]) : s_hdr[i]; };
+  // The tagged float32 kernels at a forced occupancy (WV) are no longer store-bound and take it too.
+  auto hv = [&](int i) { return (FMT == FMT_CT4 || FMT == FMT_CT8 || WV > 0) ? uni(s_hdr[i]) : s_hdr[i]; };
   const FrameHdr hc{hv(0), hv(1), hv(2), hv(3)};
   const FrameHdr hp{hv(4), hv(5), hv(6), hv(7)};
   const float gx = hv(8), gy = hv(9);
@@ -1289,7 +1323,7 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
 // TG: nothing, or one TagArgs (granule tags; an instantiation of its own, so that the launches
 // without tags keep their code)
 template <bool NT, bool XCD, bool FLOW, int FMT, class... TG>
-__global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES : 1)) void raster_kernel(ffmp_cfg_t cfg, int64_t n, int32_t bpe,
+__global__ __launch_bounds__(256, (kTagWaves<TG...> ? kTagWaves<TG...> : FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES : 1)) void raster_kernel(ffmp_cfg_t cfg, int64_t n, int32_t bpe,
                                                      int32_t cells_per_block,
                                                      const float* __restrict__ record,
                                                      const uint8_t* __restrict__ mask,
@@ -1313,7 +1347,7 @@ __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES 
     tc = stage_tags(first_arg(tg...), e, qbeg, min(qbeg + cells_per_block, cfg.grid * cfg.grid), tile_log2r, s_tags,
                     (int)threadIdx.x, 256);
   }
-  raster_env<NT, FLOW, FMT, false, TAGS>(cfg, e, tile, cells_per_block, record, state_m, sm_stride, sm_frame, newest_only,
+  raster_env<NT, FLOW, FMT, false, TAGS, kTagWaves<TG...>>(cfg, e, tile, cells_per_block, record, state_m, sm_stride, sm_frame, newest_only,
                                          pot, flow, tile_log2r, s_cur, s_prev, s_vel, s_hdr, tc);
 #ifdef FFMP_TRACE
   __syncthreads();
@@ -1330,11 +1364,13 @@ __global__ __launch_bounds__(256, (FMT == FMT_CT8 && !FLOW ? FFMP_CT8_MIN_WAVES 
 // raster's occupancy, which the compact store streams need (profiles/r02_occupancy.txt); the env
 // phase then keeps 20 B/lane of scratch, the same as the stand-alone env kernel.  Otherwise the
 // env phase's registers (89) would leave the raster 5 waves per SIMD.
-template <bool FLOW, int FMT>
-constexpr int kFusedMinWaves = (FMT == FMT_CT4 && !FLOW) ? 7 : (FMT == FMT_CT8 && !FLOW) ? FFMP_CT8_MIN_WAVES : 1;
+// Tagged float32 with FFMP_RASTER_WAVES: the W asked for (WV); its env phase falls under the same rule
+// (one beam at a time); no scratch in either phase.
+template <bool FLOW, int FMT, int WV = 0>
+constexpr int kFusedMinWaves = WV ? WV : (FMT == FMT_CT4 && !FLOW) ? 7 : (FMT == FMT_CT8 && !FLOW) ? FFMP_CT8_MIN_WAVES : 1;
 
 template <bool NT, bool XCD, bool FLOW, int FMT, bool CMD = false, class... TG>
-__global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
+__global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT, kTagWaves<TG...>>)) void step_raster_kernel(ffmp_cfg_t cfg, int64_t n, int64_t env_offset,
                                                           const act_t<CMD>* __restrict__ action, ffmp_state_t st,
                                                           ffmp_obs_t ob, ffmp_out_t out, int64_t sm_stride,
                                                           int64_t sm_frame, int32_t newest_only,
@@ -1357,7 +1393,7 @@ __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_
     stage_footprint(cfg, s_foot);
     // (one beam at a time where the block is held to more than 4 waves per SIMD: the chunked
     // lidar's registers would spill there)
-    env_group<kEnvMode_Step, 64, (kFusedMinWaves<FLOW, FMT> > 4 ? 1 : FFMP_BEAM_CHUNK), false, 1, CMD>(cfg, env_offset, action, 0, st, ob, out, e, (int)threadIdx.x, s_ox, s_oy, s_or,
+    env_group<kEnvMode_Step, 64, (kFusedMinWaves<FLOW, FMT, kTagWaves<TG...>> > 4 ? 1 : FFMP_BEAM_CHUNK), false, 1, CMD>(cfg, env_offset, action, 0, st, ob, out, e, (int)threadIdx.x, s_ox, s_oy, s_or,
                                  s_orr, s_ecur, s_eprev, s_foot, s_hdr, FLOW ? s_vel : nullptr);
   }
   // The record reaches the raster through LDS: env_group left its ego discs of both frames in
@@ -1365,7 +1401,7 @@ __global__ __launch_bounds__(256, (kFusedMinWaves<FLOW, FMT>)) void step_raster_
   // stored to st.record — so the raster starts without a round trip to HBM for them.
   __syncthreads();
   FFMP_RAS_STAMP(3);
-  raster_env<NT, FLOW, FMT, true, TAGS>(cfg, e, 0, cfg.grid * cfg.grid, st.record, ob.state_m, sm_stride, sm_frame,
+  raster_env<NT, FLOW, FMT, true, TAGS, kTagWaves<TG...>>(cfg, e, 0, cfg.grid * cfg.grid, st.record, ob.state_m, sm_stride, sm_frame,
                                         newest_only, ob.potential, ob.flow, tile_log2r, s_ecur, s_eprev, s_vel, s_hdr, tc);
 #ifdef FFMP_TRACE
   __syncthreads();
@@ -1856,6 +1892,13 @@ int raster_format(bool compact, int grid, int32_t flags) {
   return grid % 16 == 0 ? FMT_CT16 : FMT_CT4;
 }
 
+// FFMP_RASTER_WAVES -> the W of the tagged float32 kernel to launch (0: the plain one).  Without tags, in
+// the compact format or with flow planes the flag is ignored.
+int raster_waves(int32_t flags, bool tagged, bool ct, bool flow) {
+  if (!tagged || ct || flow) return 0;
+  return (flags & FFMP_RASTER_WAVES) ? kRasterWaves : 0;
+}
+
 // The granule tags behind an ffmp_obs_t with FFMP_OBS_EXT_TAGS (include/ffmp.h ffmp_obs_tags_t), checked;
 // *on = false without the flag.
 int obs_tags(const ffmp_cfg_t* cfg, const ffmp_obs_t* o, TagArgs* t, bool* on) {
@@ -2183,6 +2226,7 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
   const int32_t newest = (flags & FFMP_RASTER_NEWEST) ? 1 : 0;
   // 2-D wave tiles: R rows x 256/R columns, where the plane and the block split into them
   const int fmt = raster_format(ct, cfg->grid, flags);
+  const int waves = raster_waves(flags, tagged, ct, fl);
   // 2-D wave tiles: R rows x (cells per wave task)/R columns, where the plane and the block split into them
   int32_t tile_log2r = tile_rows_log2(flags);
   if (tile_log2r) {
@@ -2205,9 +2249,15 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
       if constexpr (decltype(FMT_)::value == FMT_F32) {
         if (tagged) {
           const TagArgs tg{tags.older + e0 * tags.env_stride, tags.newest + e0 * tags.env_stride, tags.env_stride};
-          hipLaunchKernelGGL((raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, TagArgs>),
-                             grid, block, tuning().lds_pad, s, *cfg, m, bpe, cpb, rec, msk, sm, sm_stride, sm_frame, newest,
-                             pot, flw, tile_log2r, tg);
+          auto launch = [&](auto t) {
+            hipLaunchKernelGGL((raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, decltype(t)>),
+                               grid, block, tuning().lds_pad, s, *cfg, m, bpe, cpb, rec, msk, sm, sm_stride, sm_frame, newest,
+                               pot, flw, tile_log2r, t);
+          };
+          if constexpr (!decltype(FL_)::value) {
+            if (waves == kRasterWaves) return launch(TagArgsW<kRasterWaves>{tg});
+          }
+          launch(tg);
           return;
         }
       }
@@ -2294,6 +2344,7 @@ static int step_fused(bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   const bool xcd = (flags & FFMP_RASTER_XCD) != 0;
   const int32_t newest = (flags & FFMP_RASTER_NEWEST) ? 1 : 0;
   const int fmt = raster_format(ct, cfg->grid, flags);
+  const int waves = raster_waves(flags, tagged, ct, fl);
   int32_t tile_log2r = tile_rows_log2(flags);
   if (tile_log2r && (cfg->grid % ((fmt == FMT_CT16 ? 1024 : fmt == FMT_CT8 ? 512 : 256) >> tile_log2r)) != 0)
     tile_log2r = 0;  // a block is one whole plane
@@ -2303,14 +2354,20 @@ static int step_fused(bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   dispatch_variant(fmt, nt, xcd, fl, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
     if constexpr (decltype(FMT_)::value == FMT_F32) {
       if (tagged) {
-        if (cmd)
-          hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, true, TagArgs>),
-                             grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const double2*>(action), *state,
-                             *obs, o, sm_stride, sm_frame, newest, tile_log2r, tags);
-        else
-          hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, false, TagArgs>),
-                             grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const int64_t*>(action), *state,
-                             *obs, o, sm_stride, sm_frame, newest, tile_log2r, tags);
+        auto launch = [&](auto t) {
+          if (cmd)
+            hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, true, decltype(t)>),
+                               grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const double2*>(action), *state,
+                               *obs, o, sm_stride, sm_frame, newest, tile_log2r, t);
+          else
+            hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, false, decltype(t)>),
+                               grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const int64_t*>(action), *state,
+                               *obs, o, sm_stride, sm_frame, newest, tile_log2r, t);
+        };
+        if constexpr (!decltype(FL_)::value) {
+          if (waves == kRasterWaves) return launch(TagArgsW<kRasterWaves>{tags});
+        }
+        launch(tags);
         return;
       }
     }
@@ -2447,6 +2504,17 @@ int ffmp_step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const
                      int32_t cells_per_block, int32_t flags, void* stream) {
   return step_skewed(cfg, n, env_offset, action_next, state_next, obs, out, record_raster, cells_per_block, flags,
                      stream, false);
+}
+
+int ffmp_raster_waves(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t flags) {
+  int rc = check_cfg(cfg);
+  if (rc) return rc;
+  if (!obs) return fail(FFMP_E_ARG, "obs is NULL");
+  if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
+  TagArgs tags{};
+  bool tagged = false;
+  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
+  return raster_waves(flags, tagged, obs->format == FFMP_OBS_U8F16, cfg->flow != 0);
 }
 
 int ffmp_step_skewed_check(const ffmp_cfg_t* cfg, int32_t format, int32_t flags) {

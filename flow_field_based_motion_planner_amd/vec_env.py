@@ -589,6 +589,10 @@ class FFMPVec:
         # (2.265 ms against 2.345 without the remap and 2.39 for 8,192-cell blocks;
         # profiles/r03b_transient_shapes.txt, steady state)
         (4096, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4), (4096, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE2),
+        # granule tags only: the tagged kernel held to 6 waves per SIMD (RASTER_WAVES)
+        (4096, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4 | _abi.RASTER_WAVES),
+        (8192, _abi.RASTER_NT | _abi.RASTER_TILE4 | _abi.RASTER_WAVES),
+        (16384, _abi.RASTER_NT | _abi.RASTER_TILE2 | _abi.RASTER_WAVES), (4096, _abi.RASTER_NT | _abi.RASTER_WAVES),
     )
 
     def _raster_gbs_steady(self, steps: int = 3) -> Dict[bool, Tuple[float, float]]:
@@ -912,6 +916,12 @@ class FFMPVec:
         _abi.RASTER_NT | _abi.RASTER_TILE4, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4,
         _abi.RASTER_PLAIN | _abi.RASTER_TILE4, _abi.RASTER_NT | _abi.RASTER_TILE2,
         _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE2, _abi.RASTER_NT | _abi.RASTER_TILE8,
+        # granule tags only: the TILE4 / TILE2 / row-run candidates again, held to 6 waves per SIMD
+        # (RASTER_WAVES; profiles/fused_waves_variants.json)
+        _abi.RASTER_NT | _abi.RASTER_TILE4 | _abi.RASTER_WAVES,
+        _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4 | _abi.RASTER_WAVES,
+        _abi.RASTER_PLAIN | _abi.RASTER_TILE4 | _abi.RASTER_WAVES, _abi.RASTER_NT | _abi.RASTER_TILE2 | _abi.RASTER_WAVES,
+        _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE2 | _abi.RASTER_WAVES, _abi.RASTER_NT | _abi.RASTER_WAVES,
     )
 
     # The compact format (obs_format="u8f16") writes 3 bytes per cell and is bound by the per-task
@@ -952,15 +962,21 @@ class FFMPVec:
 
     # With granule tags the 8-row tiles (32-cell row segments, half a granule) store every cell and
     # leave tag 1 behind, which would also make the next candidate's first ring cycle dense: dropped.
+    # The RASTER_WAVES forms select a kernel of their own only with tags (float32 frames, no flow
+    # planes); elsewhere the library ignores the flag, so they would time a candidate twice: dropped.
+    def _offered(self, flags: int) -> bool:
+        tags = self.frame_tags is not None
+        if flags & _abi.RASTER_WAVES and not (tags and self.obs_format == "f32" and not self.cfg.flow):
+            return False
+        return (self.XCD_SHAPES or not flags & _abi.RASTER_XCD) and not (tags and flags & _abi.RASTER_TILE8)
+
     def _shape_candidates(self):
         shapes = self.COMPACT_SHAPES if self.obs_format == "u8f16" else self.RASTER_SHAPES
-        return [sh for sh in shapes if (self.XCD_SHAPES or not sh[1] & _abi.RASTER_XCD)
-                and not (self.frame_tags is not None and sh[1] & _abi.RASTER_TILE8)]
+        return [sh for sh in shapes if self._offered(sh[1])]
 
     def _fused_candidates(self):
         flags = self.COMPACT_FUSED_FLAGS if self.obs_format == "u8f16" else self.FUSED_FLAGS
-        return [f for f in flags if (self.XCD_SHAPES or not f & _abi.RASTER_XCD)
-                and not (self.frame_tags is not None and f & _abi.RASTER_TILE8)]
+        return [f for f in flags if self._offered(f)]
 
     def _warm_tags(self) -> None:
         """One untimed ring cycle of real steps, so that every slot a timed step overwrites holds a

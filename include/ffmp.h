@@ -351,6 +351,11 @@ int ffmp_raster(const ffmp_cfg_t* cfg, int64_t n, const float* record,
 #define FFMP_RASTER_MID8 512   /* FFMP_OBS_U8F16, G % 8 == 0: 8 cells per lane (512-cell wave tasks: an
                                   8-B frame and a 16-B potential store per lane; tiles R x 512/R);
                                   NARROW wins when both are set */
+#define FFMP_RASTER_WAVES 1024 /* float32 frames with granule tags, no flow planes (ffmp_raster_ex,
+                                  ffmp_step_fused / _cmd): the kernel held to 6 waves per SIMD instead of
+                                  the 4 its registers allow.  Identical results.  Ignored without tags,
+                                  in the compact format, with flow planes and by ffmp_step_skewed
+                                  (ffmp_raster_waves tells). */
 int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record,
                    const uint8_t* mask, ffmp_obs_t* obs, int32_t cells_per_block,
                    int32_t flags, void* stream);
@@ -382,6 +387,13 @@ int ffmp_step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const
  * launches nothing.  FFMP_OK, or FFMP_E_ARG with the reason in ffmp_last_error().  A caller that
  * captures skewed step graphs asks this first (FFMPVec.capture) instead of re-deriving the LDS need. */
 int ffmp_step_skewed_check(const ffmp_cfg_t* cfg, int32_t format, int32_t flags);
+
+/* Which kernel would ffmp_raster_ex / ffmp_step_fused / ffmp_step_fused_cmd launch for these flags on this
+ * obs?  The waves per SIMD the tagged float32 kernel is held to (FFMP_RASTER_WAVES), or 0 for
+ * the plain kernel (no such flag, no tags, FFMP_OBS_U8F16 or cfg.flow).  Runs the launches' own checks of cfg
+ * and of the tag extension and their own decision, reads no device memory and launches nothing.  Negative:
+ * FFMP_E_ARG with the reason in ffmp_last_error(). */
+int ffmp_raster_waves(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t flags);
 
 /* A scripted reactive controller — no reference counterpart (the reference's actions come from its
  * Q-network, src/train.py:336-347, published as /cmd_vel :665-682) — for closed-loop runs in which
