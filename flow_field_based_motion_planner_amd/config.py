@@ -127,12 +127,37 @@ class FFMPConfig:
             raise ValueError(f"n_obst must be in [0, {MAX_OBST}], got {self.n_obst}")
         if not 0 <= self.n_beams <= MAX_BEAMS:
             raise ValueError(f"n_beams must be in [0, {MAX_BEAMS}], got {self.n_beams}")
+        # the physical constants (DESIGN.md §SPEC "Which constants are free"): finite, on the side of
+        # zero the kernels assume, and a cull margin above the float32 rounding of the culls
+        for name, v in (("res", self.res), ("dt", self.dt), ("robot_r", self.robot_r), ("goal_thr", self.goal_thr),
+                        ("world_half", self.world_half), ("lidar_max", self.lidar_max), ("k_att", self.k_att),
+                        ("k_rep", self.k_rep), ("rho0", self.rho0), ("rho_min", self.rho_min),
+                        ("cull_margin", self.cull_margin)):
+            if v is not None and not math.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v}")
         if self.res <= 0 or self.dt < 0:
             raise ValueError("res must be > 0 and dt >= 0")
+        if self.rho0 <= 0:
+            raise ValueError(f"rho0 must be > 0, got {self.rho0}")
+        if self.lidar_max is not None and self.lidar_max < 0:
+            raise ValueError(f"lidar_max must be >= 0, got {self.lidar_max}")
+        if self.robot_r < 0:
+            raise ValueError(f"robot_r must be >= 0, got {self.robot_r}")
+        if not self.cull_margin >= self.cull_floor():
+            raise ValueError(f"cull_margin must be >= {self.cull_floor():.3g} (cull_floor(): 2^-16 of the scene's "
+                             f"extent), got {self.cull_margin}")
         if not 0 <= self.seed < 2 ** 64:
             raise ValueError("seed must fit in uint64")
         if len(self.footprint) > MAX_FOOT:
             raise ValueError("footprint too large")
+
+    def cull_floor(self) -> float:
+        """The smallest cull_margin (metres) at which the raster's and the sensors' culls are exact:
+        2^-16 S with S = G res / 2 + world_half + rho0 + obst_rmax, a bound on every distance the
+        culls compare.  Fewer than 16 float32 roundings of at most 2^-24 each separate a cull's
+        distance from the cell test's, less than 2^-20 S; the floor leaves a factor of 16
+        (DESIGN.md §5 "The cull margin's floor")."""
+        return 2.0 ** -16 * (0.5 * (self.grid * self.res) + self.W + self.rho0 + self.obst_rmax)
 
     @property
     def W(self) -> float:

@@ -82,6 +82,27 @@ int check_cfg(const ffmp_cfg_t* c) {
   if (!(c->rho_min_f >= 0x1p-48f && c->rho_min_f <= 0x1p100f) || !(c->rho0_f <= 0x1p100f))
     return fail(FFMP_E_CFG, "rho_min must lie in [2^-48, 2^100] and rho0 <= 2^100");
   if (!(c->obst_rmin >= 0.0)) return fail(FFMP_E_CFG, "obst_rmin must be >= 0");
+  // the physical constants: finite, and on the side of zero the kernels assume (x - x is 0 only for a finite x)
+  const struct { const char* name; double v; } fin[] = {
+      {"res", c->res}, {"dt", c->dt}, {"robot_r", c->robot_r}, {"goal_thr", c->goal_thr},
+      {"world_half", c->world_half}, {"lidar_max", c->lidar_max}, {"k_att", (double)c->half_ka_f},
+      {"k_rep", (double)c->half_kr_f}, {"rho0", (double)c->rho0_f}, {"rho_min", (double)c->rho_min_f},
+      {"cull_margin", (double)c->cull_margin_f}};
+  for (const auto& f : fin)
+    if (!(f.v - f.v == 0.0)) return fail(FFMP_E_CFG, "%s must be finite", f.name);
+  if (!(c->res > 0.0) || !(c->dt >= 0.0)) return fail(FFMP_E_CFG, "res must be > 0 and dt >= 0");
+  if (!(c->rho0_f > 0.0f)) return fail(FFMP_E_CFG, "rho0 must be > 0, got %g", (double)c->rho0_f);
+  if (!(c->lidar_max >= 0.0)) return fail(FFMP_E_CFG, "lidar_max must be >= 0, got %g", c->lidar_max);
+  if (!(c->robot_r >= 0.0)) return fail(FFMP_E_CFG, "robot_r must be >= 0, got %g", c->robot_r);
+  // The culls are exact only with a margin above the float32 rounding of the distances they compare
+  // (DESIGN §5): cull_margin >= 2^-16 S, S = G res / 2 + world_half + rho0 + obst_rmax.  rho0 and the
+  // margin are known here as float32 only, so the floor is taken 2^-20 lower than FFMPConfig.cull_floor():
+  // a margin that FFMPConfig accepts always passes here, and the Python side stays the stricter one.
+  const double cull_floor =
+      0x1p-16 * (0.5 * (c->grid * c->res) + c->world_half + (double)c->rho0_f + c->obst_rmax) * (1.0 - 0x1p-20);
+  if (!((double)c->cull_margin_f >= cull_floor))
+    return fail(FFMP_E_CFG, "cull_margin must be >= %g (2^-16 of the scene's extent), got %g", cull_floor,
+                (double)c->cull_margin_f);
   for (int f = 0; f < c->n_foot; ++f) {
     const int i = c->grid / 2 + c->foot_di[f], j = c->grid / 2 + c->foot_dj[f];
     if (i < 0 || j < 0 || i >= c->grid || j >= c->grid)
@@ -2753,6 +2774,7 @@ int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, d
   if (!obs || !obs->grad) return fail(FFMP_E_ARG, "obs.grad is NULL");
   if (!cmd) return fail(FFMP_E_ARG, "cmd is NULL");
   if (((uintptr_t)cmd & 15u) != 0) return fail(FFMP_E_ARG, "cmd must be 16-byte aligned");
+  if (!(cfg->dt > 0.0)) return fail(FFMP_E_CFG, "ffmp_policy_field: dt must be > 0 (the turn rate divides by it), got %g", cfg->dt);
   if (n == 0) return FFMP_OK;
   if (n > 0x7fffffffLL) return fail(FFMP_E_ARG, "n too large for one launch: %lld", (long long)n);
   hipLaunchKernelGGL(policy_field_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,

@@ -907,6 +907,7 @@ int ffmp_nav_field_tiled(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs
   if (!goal_ego) return fail(FFMP_E_ARG, "%s: goal_ego is NULL", who);
   if (goal_stride < 2) return fail(FFMP_E_ARG, "%s: goal_stride must be >= 2, got %lld", who, (long long)goal_stride);
   if (((uintptr_t)cmd & 15u) != 0) return fail(FFMP_E_ARG, "%s: cmd must be 16-byte aligned", who);
+  if (cmd && !(cfg->dt > 0.0)) return fail(FFMP_E_CFG, "%s: dt must be > 0 with cmd (the follower's turn rate divides by it), got %g", who, cfg->dt);
   if (((uintptr_t)cost & 7u) != 0) return fail(FFMP_E_ARG, "%s: cost must be 8-byte aligned", who);
   if (((uintptr_t)dir & 3u) != 0) return fail(FFMP_E_ARG, "%s: dir must be 4-byte aligned", who);
   if (!workspace) return fail(FFMP_E_ARG, "%s: workspace is NULL", who);
@@ -990,6 +991,8 @@ int ffmp_nav_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, cons
   if (!goal_ego) return fail(FFMP_E_ARG, "ffmp_nav_field: goal_ego is NULL");
   if (goal_stride < 2) return fail(FFMP_E_ARG, "ffmp_nav_field: goal_stride must be >= 2, got %lld", (long long)goal_stride);
   if (((uintptr_t)cmd & 15u) != 0) return fail(FFMP_E_ARG, "ffmp_nav_field: cmd must be 16-byte aligned");
+  if (cmd && !(cfg->dt > 0.0))
+    return fail(FFMP_E_CFG, "ffmp_nav_field: dt must be > 0 with cmd (the follower's turn rate divides by it), got %g", cfg->dt);
   if (((uintptr_t)cost & 7u) != 0) return fail(FFMP_E_ARG, "ffmp_nav_field: cost must be 8-byte aligned");
   if (((uintptr_t)dir & 3u) != 0) return fail(FFMP_E_ARG, "ffmp_nav_field: dir must be 4-byte aligned");
   if (n == 0) return FFMP_OK;

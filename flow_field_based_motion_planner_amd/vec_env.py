@@ -1666,6 +1666,8 @@ class FFMPVec:
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_field()")
+        if not self.cfg.dt > 0:
+            raise ValueError("policy_field: dt must be > 0 (the turn rate divides by it)")
         if out is None:
             out = torch.empty((self.num_envs, 2), dtype=torch.float64, device=self.device)
         elif tuple(out.shape) != (self.num_envs, 2) or out.dtype != torch.float64 or not out.is_contiguous() \
@@ -2003,6 +2005,8 @@ class FFMPVec:
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_nav()")
+        if not self.cfg.dt > 0:
+            raise ValueError("policy_nav: dt must be > 0 (the follower's turn rate divides by it)")
         if out is None:
             out = torch.empty((self.num_envs, 2), dtype=torch.float64, device=self.device)
         elif tuple(out.shape) != (self.num_envs, 2) or out.dtype != torch.float64 or not out.is_contiguous() \
@@ -2391,6 +2395,8 @@ class LidarFlow:
         lag = int(lag)
         if not 1 <= lag <= self.MAX_LAG:
             raise ValueError(f"lag must be in [1, {self.MAX_LAG}], got {lag}")
+        if not env.cfg.dt > 0:
+            raise ValueError("lidar_flow: dt must be > 0 (a velocity is a displacement over lag * dt)")
         self.env, self.lag = env, lag
         self.scale = float(np.float32(env.cfg.res / (lag * env.cfg.dt)))
         self.knobs = (env._fmt, self.scale, int(radius), int(block), int(gate), int(min_hits))

@@ -102,11 +102,11 @@ typedef struct ffmp_cfg {
   int32_t foot_di[FFMP_MAX_FOOT]; /* footprint cell offsets from (G/2, G/2) */
   int32_t foot_dj[FFMP_MAX_FOOT];
   double res;            /* m per cell (ffmp.py:18, 0.05) */
-  double dt;             /* s per step */
-  double robot_r;        /* lidar collision threshold (ffmp.py:17, 0.13) */
+  double dt;             /* s per step, >= 0 (0: nothing moves; the followers that divide by it refuse it) */
+  double robot_r;        /* lidar collision threshold (ffmp.py:17, 0.13), >= 0 */
   double goal_thr;       /* goal threshold (ffmp.py:19, 0.5) */
   double world_half;     /* world is [-world_half, world_half]^2 (m) */
-  double lidar_max;      /* lidar max range (m); farther -> +inf */
+  double lidar_max;      /* lidar max range (m), >= 0; farther -> +inf */
   double goal_min, goal_max;   /* reset: goal distance range (m) */
   double obst_rmin, obst_rmax; /* reset: obstacle radius range (m) */
   double obst_vmax;            /* reset: obstacle speed range [0, vmax] (moving) */
@@ -117,11 +117,18 @@ typedef struct ffmp_cfg {
   float world_half_f;    /* (float)world_half */
   float half_ka_f;       /* (float)(0.5 * k_att) */
   float half_kr_f;       /* (float)(0.5 * k_rep) */
-  float rho0_f;          /* (float)rho0 : repulsive cut-off (m) */
+  float rho0_f;          /* (float)rho0 : repulsive cut-off (m), > 0 */
   float inv_rho0_f;      /* (float)(1.0 / rho0) */
   float rho_min_f;       /* (float)rho_min : distance clamp (m) */
   float inv_2res_f;      /* (float)(1.0 / (2.0 * res)) : central-difference scale */
-  float cull_margin_f;   /* extra culling margin (m), conservative */
+  float cull_margin_f;   /* (float)cull_margin : metres added to a disc's reach (and taken off the world's
+                          * half side) by every cull, so that a float32 rounding never culls a disc or a
+                          * wall a cell test would have seen.  Must be finite and at least
+                          * 2^-16 S, S = G res / 2 + world_half + rho0 + obst_rmax: the culls' distances
+                          * are bounded by S and differ from the cell tests' by fewer than 16 roundings
+                          * of 2^-24 each (< 2^-20 S); the floor leaves a factor of 16 (3e-4 m at
+                          * G = 256, res = 0.05; the default is 0.1).  Below it: FFMP_E_CFG.  A larger
+                          * margin costs time only, never a bit of the planes. */
   uint64_t seed;         /* Philox4x32-10 key */
   const double* beam_cs; /* DEVICE (L,2) float64 {cos, sin} of beam angle -pi + l*2pi/L, 16-B aligned */
 } ffmp_cfg_t;
@@ -445,7 +452,8 @@ int ffmp_step_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const do
  *         if dx < 0:  w = dy >= 0 ? 0.6 : -0.6                 (descent points behind: turn on the spot)
  *         v = 0.6 * (dx > 0 ? dx : 0.0)
  * cmd: (n, 2) float64 device memory, 16-byte aligned — what the *_cmd steps read.  obs->grad or cmd
- * NULL, cmd misaligned: FFMP_E_ARG; n == 0: nothing is launched.  One lane per env. */
+ * NULL, cmd misaligned: FFMP_E_ARG; cfg->dt == 0 (w divides by it): FFMP_E_CFG; n == 0: nothing is
+ * launched.  One lane per env. */
 int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, double* cmd, void* stream);
 
 /* A navigation field (an addition within ABI 9: no existing symbol, struct or value changes) — no
@@ -494,6 +502,8 @@ int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, d
  * obs->state_m or goal_ego NULL; goal_stride < 2; cmd not 16-byte, cost not 8-byte or dir not 4-byte
  * aligned; an unknown obs format; n < 0.  n == 0: nothing is launched.  Obstacle velocities are not
  * looked at (a static plan over the newest frame), and the follower is stateless.
+ * cmd given with cfg->dt == 0 (the follower's turn rate divides by it): FFMP_E_CFG; the planes alone
+ * need no dt.
  * ffmp_nav_field_check: the checks that need no pointer (shape, format, knobs, LDS budget), no launch. */
 int ffmp_nav_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs,
                    const float* goal_ego, int64_t goal_stride /* floats between envs */,

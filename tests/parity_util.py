@@ -10,6 +10,55 @@ F32_OBS_ATOL = 1e-5        # state_g, state_v, state_t, grad, reward, lidar (flo
 POT_RTOL, POT_ATOL = 1e-6, 1e-5
 
 
+# every array of an oracle env (OracleVecEnv, COracleVecEnv), for same_bits
+ORACLE_ARRAYS = ("pose", "goal", "d0", "obst", "obst_r", "t", "episode", "record", "term_record", "term_obs", "state_m",
+                 "potential", "state_g", "state_v", "state_t", "grad", "lidar", "reward", "done", "is_goal", "collision",
+                 "truncated")
+
+
+def same_bits(a, b, tag):
+    """Two oracle envs hold the same arrays, bit for bit (NaN / -0 too), and the same err."""
+    for name in ORACLE_ARRAYS + (("flow",) if a.cfg.flow else ()):
+        x, y = getattr(a, name), getattr(b, name)
+        assert x.dtype == y.dtype and x.shape == y.shape, (tag, name)
+        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (tag, name)
+    assert a.err == b.err, tag
+
+
+def run_parity(cfg, n, steps, seed=0, env_offset=0, keep_terminal=True, frame_window=None, fused=None, fused_flags=None,
+               **env_kw):
+    """Step an FFMPVec on cuda:0 and the NumPy oracle side by side over rng(seed) actions, comparing
+    after the reset and after every step: (env, ref, mismatches, event counts).  env_kw: further
+    FFMPVec arguments."""
+    import torch
+
+    from flow_field_based_motion_planner_amd.vec_env import FFMPVec
+    from oracle.ffmp_oracle import OracleVecEnv
+    env = FFMPVec(n, cfg, device="cuda:0", env_offset=env_offset, keep_terminal=keep_terminal,
+                  frame_window=frame_window, fused=fused, **env_kw)
+    if fused_flags is not None:
+        env.fused_flags = fused_flags
+    ref = OracleVecEnv(cfg, n, env_offset=env_offset)
+    env.reset()
+    ref.reset()
+    torch.cuda.synchronize()
+    problems = compare(gpu_snapshot(env), oracle_snapshot(ref), "reset")
+    rng = np.random.default_rng(seed)
+    counts = {"done": 0, "collision": 0, "goal": 0, "trunc": 0}
+    for s in range(steps):
+        a = rng.integers(0, 28, n)
+        env.step(torch.as_tensor(a, device="cuda:0"))
+        ref.step(a)
+        torch.cuda.synchronize()
+        g = gpu_snapshot(env)
+        problems += compare(g, oracle_snapshot(ref), f"step {s}")
+        counts["done"] += int(g["done"].sum())
+        counts["collision"] += int(g["collision"].sum())
+        counts["goal"] += int(g["is_goal"].sum())
+        counts["trunc"] += int(g["truncated"].sum())
+    return env, ref, problems, counts
+
+
 def gpu_snapshot(env, sl=slice(None)):
     d = {k: getattr(env, k)[sl].detach().cpu().numpy() for k in
          ("state_m", "state_g", "state_v", "state_t", "grad", "reward", "done", "is_goal", "collision",
@@ -151,3 +200,17 @@ def network_inputs(batch, seed):
     t = rng.uniform(0.0, 0.2, (batch, 1)).astype(np.float32)
     return sm, g, v, t
 
+
+
+def policy_reactive_np(cfg, newest, state_g):
+    """ffmp_policy_reactive restated (include/ffmp.h): newest (N, G, G), state_g (N, 2) float32."""
+    G = cfg.grid
+    look0, look1 = 3, min(3 + int(round(0.25 / cfg.res)), G // 2 - 1)
+    orient = state_g[:, 1].astype(np.float32)
+    wi = np.clip(np.rint(orient / np.float32(0.2)).astype(np.int64) + 3, 0, 6)
+    ray = newest[:, G // 2 + look0:G // 2 + look1 + 1, G // 2]
+    blocked = (ray > 0).any(1)
+    vi = np.where(state_g[:, 0] < np.float32(1.0), 1, 3)
+    vi = np.where(blocked, 0, vi)
+    wi = np.where(blocked & (wi == 3), 6, wi)
+    return 7 * vi + wi

@@ -12,6 +12,7 @@ from flow_field_based_motion_planner_amd import FFMPConfig, preset
 from flow_field_based_motion_planner_amd.vec_env import FFMPVec
 from oracle.ffmp_oracle import OracleVecEnv, Record, raster
 from tests.parity_util import compare, exact_report, gpu_snapshot, oracle_snapshot
+from tests.parity_util import run_parity as _run
 
 pytestmark = pytest.mark.gpu
 
@@ -28,32 +29,6 @@ CASES = {
     "flow_planes": (FFMPConfig(grid=128, n_obst=24, n_beams=64, moving=True, flow=True, obst_rmax=0.7,
                                obst_vmax=1.2, seed=8), 12, 15),
 }
-
-
-def _run(cfg, n, steps, seed=0, env_offset=0, keep_terminal=True, frame_window=None, fused=None, fused_flags=None):
-    env = FFMPVec(n, cfg, device="cuda:0", env_offset=env_offset, keep_terminal=keep_terminal,
-                  frame_window=frame_window, fused=fused)
-    if fused_flags is not None:
-        env.fused_flags = fused_flags
-    ref = OracleVecEnv(cfg, n, env_offset=env_offset)
-    env.reset()
-    ref.reset()
-    torch.cuda.synchronize()
-    problems = compare(gpu_snapshot(env), oracle_snapshot(ref), "reset")
-    rng = np.random.default_rng(seed)
-    counts = {"done": 0, "collision": 0, "goal": 0, "trunc": 0}
-    for s in range(steps):
-        a = rng.integers(0, 28, n)
-        env.step(torch.as_tensor(a, device="cuda:0"))
-        ref.step(a)
-        torch.cuda.synchronize()
-        g = gpu_snapshot(env)
-        problems += compare(g, oracle_snapshot(ref), f"step {s}")
-        counts["done"] += int(g["done"].sum())
-        counts["collision"] += int(g["collision"].sum())
-        counts["goal"] += int(g["is_goal"].sum())
-        counts["trunc"] += int(g["truncated"].sum())
-    return env, ref, problems, counts
 
 
 @pytest.mark.parametrize("name", list(CASES))

@@ -7,23 +7,13 @@ import pytest
 from flow_field_based_motion_planner_amd.config import FFMPConfig, preset
 from oracle import ffmp_oracle_c as oc
 from oracle.ffmp_oracle import OracleVecEnv
-
-ARRAYS = ("pose", "goal", "d0", "obst", "obst_r", "t", "episode", "record", "term_record", "term_obs", "state_m",
-          "potential", "state_g", "state_v", "state_t", "grad", "lidar", "reward", "done", "is_goal", "collision",
-          "truncated")
+from tests.parity_util import ORACLE_ARRAYS as ARRAYS  # noqa: F401
+from tests.parity_util import same_bits as _same
 
 
 @pytest.fixture(scope="module", autouse=True)
 def built():
     oc.build()
-
-
-def _same(a, b, tag):
-    for name in ARRAYS + (("flow",) if a.cfg.flow else ()):
-        x, y = getattr(a, name), getattr(b, name)
-        assert x.dtype == y.dtype and x.shape == y.shape, (tag, name)
-        assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (tag, name)  # bit for bit (NaN / -0 too)
-    assert a.err == b.err, tag
 
 
 CASES = {
