@@ -161,6 +161,10 @@ _SIGS = {
     "ffmp_scan_flow": (C.c_int, [C.POINTER(CfgT), _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32,
                                  C.c_float, _I32, _I32, _I32, _I32, _P]),
     "ffmp_scan_flow_check": (C.c_int, [C.POINTER(CfgT), _I32, C.c_float, _I32, _I32, _I32, _I32]),
+    # predicted-occupancy frames from a frame and its flow (an addition within ABI 9): the planner's view of the flow
+    "ffmp_flow_predict": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _I64, _P, _I32,
+                                    C.c_float, _I32, _I32, _I32, _I32, _P]),
+    "ffmp_flow_predict_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, _I32, _I32, _I32, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

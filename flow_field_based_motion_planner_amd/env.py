@@ -417,6 +417,14 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before lidar_flow()")
         return self._vec_env().lidar_flow(**kw)
 
+    def predicted_frames(self, **kw):
+        """The predicted-occupancy frame of this one env (FFMPVec.predicted_frames, include/ffmp.h
+        ffmp_flow_predict): a device tensor (1, G, G) uint8 — and n_swept (1,) int32 with count=True —,
+        the plane nav_field(predict=...) plans over."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before predicted_frames()")
+        return self._vec_env().predicted_frames(**kw)
+
     def render(self, mode="human"):
         return None
 

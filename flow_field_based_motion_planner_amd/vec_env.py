@@ -29,6 +29,7 @@ step's return value (or `env.state_m`) rather than keeping the first one.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Dict, Optional, Tuple, Union
 
@@ -1735,15 +1736,32 @@ class FFMPVec:
     def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
                     cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None,
                     frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False,
-                    lidar_map: Optional["LidarMap"] = None) -> None:
+                    lidar_map: Optional["LidarMap"] = None, predict=False) -> None:
         """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
         observation: the newest frame through the window's strides and format, the ego goal from
         record words 8..9.  frames: plan over this (N, G, G) plane instead of the newest frame;
         visible: over visible_frames(newest_only=True, unknown=0); lidar: over
-        lidar_frames(newest_only=True, unknown=0); lidar_map: over that LidarMap's frame."""
+        lidar_frames(newest_only=True, unknown=0); lidar_map: over that LidarMap's frame; predict:
+        over predicted_frames() (True), predicted_frames(**predict) (a dict) or
+        predicted_frames(flow=predict) (a LidarFlow)."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError(f"call reset() before {what}()")
+        if predict is not False and predict is not None:
+            if frames is not None or visible or lidar or lidar_map is not None:
+                raise ValueError(f"{what}: pass one of frames, visible=True, lidar=True, lidar_map and predict")
+            if predict is True:
+                kw = {}
+            elif isinstance(predict, dict):
+                kw = dict(predict)
+                if kw.get("count") or kw.get("out") is not None:
+                    raise ValueError(f"{what}: predict takes predicted_frames' knobs, not out= or count=")
+            elif isinstance(predict, LidarFlow):
+                kw = {"flow": predict}
+            else:
+                raise ValueError(f"{what}: predict must be False, True, a dict of predicted_frames' keyword arguments "
+                                 f"or a LidarFlow of this env")
+            frames = self.predicted_frames(**kw)
         if visible:
             if frames is not None:
                 raise ValueError(f"{what}: pass frames or visible=True, not both")
@@ -1944,10 +1962,91 @@ class FFMPVec:
         return LidarFlow(self, lag, radius, block, gate, min_hits, self.cfg.res if thickness is None else thickness,
                          self.cfg.lidar_range if range_max is None else range_max, kind)
 
+    # ------------------------------------------------ predicted-occupancy frames
+    def predicted_frames(self, flow=None, frames: Optional[torch.Tensor] = None, steps: int = 24, slack: int = 3,
+                         dt: Optional[float] = None, speed: float = 0.6, swept: int = 254, other: int = 128,
+                         out: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, count: bool = False):
+        """The newest frame with the cells a moving obstacle is predicted to cover when the robot can be
+        there marked occupied, on the device (include/ffmp.h ffmp_flow_predict): (N, G, G) uint8 — 255
+        where the frame is 255, `other` where it holds another value > 0, `swept` where a predicted cell
+        is free now, else 0 — the plane nav_field(predict=...) plans over.  Every 255 cell with a
+        velocity is moved along it for k = 1..`steps` prediction steps of `dt` seconds (default
+        cfg.dt) and blocks its target cell if the robot, covering `speed` m/s, could reach that cell
+        within `slack` steps of step k (its chamfer distance from the robot cell at
+        pace = max(1, rint(5 * speed * dt / res)) units per step); slack=-1 blocks the whole swept
+        corridor.  Present occupancy always stays.
+        flow: None — the env's own obs["flow"] over the newest frame (the env must have been made
+        with flow=True); a contiguous (N, 2, G, G) float32 or float16 device tensor [vx, vy] in m/s
+        in the current ego axes; or a LidarFlow of this env — its .flow over its .frame.  frames: a
+        contiguous (N, G, G) float32 or uint8 device tensor instead of that frame.  out: write into
+        this contiguous (N, G, G) uint8 tensor; mask: (N,) bool or uint8, envs with 0 keep their
+        cells of `out`; count=True: also return n_swept (N,) int32, the free cells newly blocked.
+        One launch on the current stream, so a caller can capture it into a graph of their own; the
+        step and its frames are untouched.  Known limits: constant velocities (no wall reflection, no
+        reaction to the robot); a thin arc faster than about two cells per step leaves one-cell gaps
+        that nav_field's footprint dilation closes; the arrival time is a straight-line bound."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before predicted_frames()")
+        n, G = self.num_envs, self.cfg.grid
+        G2 = G * G
+        plane = None
+        if isinstance(flow, LidarFlow):
+            if flow.env is not self:
+                raise ValueError("predicted_frames: flow must be a LidarFlow of this env")
+            plane, flow = flow.frame, flow.flow
+        elif flow is None:
+            if self.flow is None:
+                raise ValueError("predicted_frames: the env was made without flow=True, pass flow=")
+            flow = self.flow
+        elif not isinstance(flow, torch.Tensor) or tuple(flow.shape) != (n, 2, G, G) \
+                or flow.dtype not in (torch.float32, torch.float16) or not flow.is_contiguous() or flow.device != self.device:
+            raise ValueError(f"flow must be a contiguous float32 or float16 tensor of shape ({n}, 2, {G}, {G}) on {self.device}, "
+                             f"or a LidarFlow of this env")
+        fmts = {torch.float32: _abi.OBS_F32, torch.uint8: _abi.OBS_U8F16}
+        if frames is not None:
+            if not isinstance(frames, torch.Tensor) or tuple(frames.shape) != (n, G, G) or frames.dtype not in fmts \
+                    or not frames.is_contiguous() or frames.device != self.device:
+                raise ValueError(f"frames must be a contiguous float32 or uint8 tensor of shape ({n}, {G}, {G}) on {self.device}")
+            plane = frames
+        elif plane is None:
+            plane = self.state_m[:, 1]  # a view: the env stride of the window
+        if dt is None:
+            dt = self.cfg.dt
+        dt, res, speed = float(dt), float(self.cfg.res), float(speed)
+        if not (math.isfinite(dt) and dt > 0):
+            raise ValueError(f"predicted_frames: dt must be finite and > 0, got {dt}")
+        with np.errstate(over="ignore"):
+            cps = float(np.float32(dt / res))
+        if not (math.isfinite(cps) and cps > 0):
+            raise ValueError(f"predicted_frames: dt / res = {dt} / {res} is not a finite positive float32 (res)")
+        if not (math.isfinite(speed) and speed >= 0):
+            raise ValueError(f"predicted_frames: speed must be finite and >= 0, got {speed}")
+        pace = 5.0 * speed * dt / res
+        if not pace <= 1024:
+            raise ValueError(f"predicted_frames: speed * dt / res gives a pace of {pace:.6g} chamfer units per step, above 1024 (speed)")
+        pace = max(1, int(np.rint(pace)))
+        knobs = (int(steps), cps, pace, int(slack), int(swept), int(other))
+        ffmt, vfmt = fmts[plane.dtype], _abi.OBS_F32 if flow.dtype == torch.float32 else _abi.OBS_U8F16
+        _abi.check(self.lib.ffmp_flow_predict_check(C.byref(self._cfg_c), ffmt, vfmt, *knobs), "ffmp_flow_predict_check")
+        if out is None:
+            out = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, G, G) or out.dtype != torch.uint8 \
+                or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out must be a contiguous uint8 tensor of shape ({n}, {G}, {G}) on {self.device}")
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=self.device).reshape(n).to(torch.uint8).contiguous()
+        n_swept = torch.zeros(n, dtype=torch.int32, device=self.device) if count else None
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_flow_predict(C.byref(self._cfg_c), n, plane.data_ptr(), plane.stride(0), ffmt,
+                                                  flow.data_ptr(), flow.stride(0), vfmt, _ptr(mask), out.data_ptr(), G2,
+                                                  _ptr(n_swept), *knobs, self._stream()), "ffmp_flow_predict")
+        return (out, n_swept) if count else out
+
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
                   lookahead: int = 4, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
-                  visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None
-                  ) -> Dict[str, torch.Tensor]:
+                  visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None,
+                  predict=False) -> Dict[str, torch.Tensor]:
         """The navigation field of the current observation, on the device (include/ffmp.h
         ffmp_nav_field): the cost-to-go from the goal cell over the traversable cells of the newest
         ego frame (hard = the footprint-dilated occupancy; a `margin`-cell zone around it costs
@@ -1959,7 +2058,8 @@ class FFMPVec:
                    ~8 %), with the zone's penalties included
           cost (N, G, G) uint16 (65535: hard or unreachable) with cost=True
           dir  (N, G, G) uint8 (neighbour index 0..7, 8 at the goal, 255 unreachable) with direction=True
-        A static plan: obstacle velocities are not looked at.  Grids up to 512 x 512: up to
+        A static plan over the plane it is given: obstacle velocities are looked at only with
+        predict= (below).  Grids up to 512 x 512: up to
         256 x 256 one workgroup holds an env's whole plane in LDS; above that, or when `tile` (or the
         attribute nav_tile) is given, the plane lives in a workspace on the device and is relaxed in
         tiles of `tile` x `tile` cells (0 = the library's default, 256; else a multiple of 32 in
@@ -1970,7 +2070,11 @@ class FFMPVec:
         can see with hidden cells taken as free (the usual free-space assumption); lidar=True: over
         lidar_frames(newest_only=True, unknown=0), the map made from the scan alone, what a real
         robot has; lidar_map=m: over m.frame, the accumulated map of a LidarMap of this env (make it
-        with unknown=0 to count unknown cells as free; the caller updates it).  At most one of the four.
+        with unknown=0 to count unknown cells as free; the caller updates it); predict: over
+        predicted_frames(), the newest frame with the cells a moving obstacle is predicted to cover
+        when the robot can be there marked occupied — True for its defaults, a dict of its keyword
+        arguments, or a LidarFlow of this env for that holder's frame and estimated flow (grids up to
+        512 x 512; one more launch).  At most one of the five.
         Inside a graph capture of the caller's: call it once eagerly first, with the same tile and
         cost= (the tiled kernel's workspace is allocated and its kernel set up at the first such
         call; lidar=True also builds lidar_frames' sector table then)."""
@@ -1983,20 +2087,23 @@ class FFMPVec:
             out["dir"] = torch.empty((n, G, G), dtype=torch.uint8, device=self.device)
         self._nav_launch("nav_field", margin, soft_pen, lookahead, self.NAV_DEFAULTS["turn_sin"],
                          cost=out.get("cost"), direction=out.get("dir"), target=out["target"], geo_cost=out["geo_cost"],
-                         tile=tile, frames=frames, visible=visible, lidar=lidar, lidar_map=lidar_map)
-        gc = out["geo_cost"].to(torch.float64)
+                         tile=tile, frames=frames, visible=visible, lidar=lidar, lidar_map=lidar_map, predict=predict)
+        gc =out["geo_cost"].to(torch.float64)
         out["geo_dist"] = torch.where(gc < 0, torch.full_like(gc, float("inf")), gc * (self.cfg.res / 5.0))
         return out
 
     def policy_nav(self, out: Optional[torch.Tensor] = None, margin: int = 2, soft_pen: int = 40, lookahead: int = 4,
                    turn_sin: float = 0.25, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,
-                   visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None) -> torch.Tensor:
+                   visible: bool = False, lidar: bool = False, lidar_map: Optional["LidarMap"] = None,
+                   predict=False) -> torch.Tensor:
         """The next (v, w) commands (N, 2) float64 from the navigation field of the current
         observation, on the device (include/ffmp.h ffmp_nav_field's follower): head for the cell
         `lookahead` moves down the cheapest path, turning on the spot while it lies more than
         asin(turn_sin) off the heading.  Complete on a static scene (it has no local minima, unlike
         policy_field); stateless, so on an exactly symmetric scene it can dither between two equal
-        routes; obstacle velocities are not looked at.  (0, 0) when the goal is unreachable.  `out`:
+        routes; obstacle velocities are looked at only with predict= (as for nav_field: the plan
+        then passes behind a crossing obstacle instead of steering for the gap it is about to fill).
+        (0, 0) when the goal is unreachable.  `out`:
         write into this (N, 2) float64 tensor (e.g. command_buffer) instead of a new one.  `tile`: as
         for nav_field (grids above 256 x 256 always take the tiled kernel); `frames`, `visible`, `lidar`,
         `lidar_map`: as for nav_field (plan over a plane of the caller's, over what the robot can see,
@@ -2014,7 +2121,7 @@ class FFMPVec:
             raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
                              f"({self.num_envs}, 2) on {self.device}")
         self._nav_launch("policy_nav", margin, soft_pen, lookahead, turn_sin, cmd=out, tile=tile, frames=frames,
-                         visible=visible, lidar=lidar, lidar_map=lidar_map)
+                         visible=visible, lidar=lidar, lidar_map=lidar_map, predict=predict)
         return out
 
     # ------------------------------------------------ HIP graph of whole steps

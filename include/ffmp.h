@@ -45,6 +45,8 @@
  *   ffmp_scan_flow      -> the flow half of that image (the RGB of "occupancy(MONO) + flow(RGB)",
  *                          src/gym_ffmp/envs/ffmp.py:16) from two scan frames and the two poses: a
  *                          per-cell velocity by block matching with ego-motion compensation [unpinned]
+ *   ffmp_flow_predict   -> what the planner makes of that flow: the frame with the cells a moving
+ *                          obstacle will cover when the robot can be there marked occupied [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -777,6 +779,62 @@ int ffmp_scan_flow(const ffmp_cfg_t* cfg, int64_t n, const uint8_t* cur, const u
                    int32_t min_hits, void* stream);
 int ffmp_scan_flow_check(const ffmp_cfg_t* cfg, int32_t format, float scale, int32_t radius, int32_t block, int32_t gate,
                          int32_t min_hits);
+
+/* Predicted-occupancy frames (an addition within ABI 9: no existing symbol, struct or value changes):
+ * the step that joins the flow planes (cfg.flow's, or ffmp_scan_flow's estimate) to ffmp_nav_field.  The
+ * cells a moving obstacle is predicted to cover at about the time the robot could be there are marked
+ * in a copy of the frame, and the navigation field planned over that copy passes behind a crossing
+ * obstacle instead of steering for the gap it is about to fill.  No reference counterpart [unpinned]; the
+ * SPEC below is the definition.
+ * SPEC, per env.  F: the frame, G x G, row i ego x, column j ego y, c = G/2.  vx, vy: the flow planes,
+ * m/s in the current ego axes, binary16 converted to float32 first.  Knobs: steps H 1..64; cps
+ * (float32, cells per m/s per prediction step: a caller passes (float)(dt_pred / res)); pace 1..1024,
+ * the chamfer units (5 per cell) the robot covers per prediction step; slack -1..255; bytes swept, other.
+ *   occ[a]  = F[a] > 0                      (a NaN compares false)
+ *   src[a]  = F[a] == 255
+ *   su = vx[a] * cps;  sv = vy[a] * cps     (one float32 multiply each, no contraction)
+ *   a source is skipped if su or sv is not finite, or both are 0
+ *   for k = 1..H:
+ *       ti = i + (int)rintf((float)k * su);  tj = j + (int)rintf((float)k * sv)     (half to even)
+ *       skipped if (ti, tj) lies outside 0..G-1
+ *       m = max(|ti-c|, |tj-c|);  n = min(|ti-c|, |tj-c|);  ka = (5*m + 2*n) / pace   (integer division)
+ *       slack < 0  or  |k - ka| <= slack :  bit[ti][tj] = 1
+ *   out[a]  = F[a] == 255 ? 255 : occ[a] ? other : bit[a] ? swept : 0                (uint8, whatever the inputs)
+ *   n_swept = number of cells with bit && !occ
+ * A rounded displacement of G cells or more (a product that overflows to infinity included) leaves
+ * the grid from any cell: it is skipped and no integer is formed for it.
+ * ka is the earliest prediction step at which the robot can stand on the cell: the chamfer 5-7
+ * distance from the robot cell at `pace` units per step.  The gate: a cell is blocked only if an
+ * obstacle is predicted there within `slack` steps of that moment, so a disc that will have passed
+ * before the robot can arrive blocks nothing.  slack = -1 turns the gate off and blocks the whole
+ * swept corridor.  Present occupancy always stays: cells a moving disc is about to vacate are not
+ * freed (conservative on purpose).
+ * Mask: an env with mask[e] == 0 keeps its cells of `out` and its n_swept.
+ * Parity: integer arithmetic apart from the two multiplies and (float)k * s, and the bits are ORed, so
+ * the order cannot matter: the kernel equals tests/flow_predict_ref.py bit for bit.
+ * Known limits: the prediction is constant-velocity (no wall reflection, no robot-obstacle
+ * interaction); a thin arc moving more than about two cells per step leaves one-cell gaps between
+ * successive k (ffmp_nav_field's footprint dilation closes those); the robot's arrival time is a
+ * straight-line bound that ignores the detour.
+ * cfg: only grid is read.  frame: DEVICE (n, G, G), env e at e * frame_env_stride elements;
+ * frame_format FFMP_OBS_F32: float32, FFMP_OBS_U8F16: uint8.  flow: DEVICE (n, 2, G, G), env e at
+ * e * flow_env_stride elements, vy = vx + G*G; flow_format FFMP_OBS_F32: float32, FFMP_OBS_U8F16:
+ * binary16 — the two formats are separate (uint8 scan frames beside float32 flow is a real
+ * combination).  mask: (n) bytes or NULL.  out: DEVICE uint8 (n, G, G), env e at e * out_env_stride
+ * bytes.  n_swept: DEVICE int32 (n) or NULL.  16-byte loads and stores are used where a plane's base
+ * and env stride allow, 4-byte ones otherwise.
+ * FFMP_E_ARG, with a message and before any HIP call, for: a grid outside 8..512 or not a multiple of
+ * 4; an unknown format; a knob out of range; cps not finite or < 0; swept or other outside 0..255;
+ * frame, flow or out NULL; a stride that is too small (frame and out G*G, flow 2*G*G); misaligned
+ * planes or strides (bases 4 bytes, strides multiples of 4 elements); an out (or n_swept) that
+ * overlaps an input; n < 0 or too large for one launch.  n == 0: nothing is launched.
+ * ffmp_flow_predict_check: the checks that need no pointer (shape, formats, knobs), no launch. */
+int ffmp_flow_predict(const ffmp_cfg_t* cfg, int64_t n, const void* frame, int64_t frame_env_stride, int32_t frame_format,
+                      const void* flow, int64_t flow_env_stride, int32_t flow_format, const uint8_t* mask, uint8_t* out,
+                      int64_t out_env_stride, int32_t* n_swept, int32_t steps, float cps, int32_t pace, int32_t slack,
+                      int32_t swept, int32_t other, void* stream);
+int ffmp_flow_predict_check(const ffmp_cfg_t* cfg, int32_t frame_format, int32_t flow_format, int32_t steps, float cps,
+                            int32_t pace, int32_t slack, int32_t swept, int32_t other);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
