@@ -123,6 +123,7 @@ _SIGS = {
                                    C.POINTER(OutT), _P, _I32, _I32, _P]),
     "ffmp_step_skewed_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32]),
     "ffmp_raster_waves": (C.c_int, [C.POINTER(CfgT), C.POINTER(ObsT), _I32]),
+    "ffmp_raster_direct": (C.c_int, [C.POINTER(CfgT), C.POINTER(ObsT), _I32, _I32]),
     "ffmp_policy_reactive": (C.c_int, [C.POINTER(CfgT), _I64, C.POINTER(ObsT), _P, _P]),
     # continuous (v, w) commands (ABI 9): the id entry points' signatures, cmd = (n, 2) float64
     "ffmp_step_state_cmd": (C.c_int, [C.POINTER(CfgT), _I64, _I64, _P, C.POINTER(StateT), C.POINTER(ObsT),
@@ -276,6 +277,7 @@ RASTER_NARROW = 128  # FFMP_OBS_U8F16: 4 cells per lane instead of 16
 RASTER_TILE16 = 256
 RASTER_MID8 = 512  # FFMP_OBS_U8F16: 8 cells per lane
 RASTER_WAVES = 1024  # float32 frames with granule tags: the kernel held to 6 waves per SIMD
+RASTER_DIRECT = 2048  # beside RASTER_WAVES, two-launch raster: blocks without LDS or barrier, one memory round trip
 VISIBLE_NOCULL = 1  # FFMP_VISIBLE_NOCULL: ffmp_visible_frames without its culls (the same bits)
 SCAN_PLAIN = 1  # FFMP_SCAN_PLAIN: ffmp_scan_frames with the SPEC's bisection for every cell (the same bits)
 

@@ -188,9 +188,20 @@ FFMP_DEV void wave_sync() {
 // stamps (100 MHz) at checkpoints of the env step (first 4096 envs, lane 0 of each env group)
 // and of the raster (first 65536 blocks, thread 0), read back by ffmp_trace_read.  Each stamp
 // first waits for the wave's outstanding memory operations, so the gaps are the chain's latency.
+// Raster stamps: 3 kernel entry, 0 block start behind the staged tags, 1 record read (staged form:
+// behind the barrier; direct form: behind its one wait), 2 block done.  FFMP_WAVE_STAMP: lane 0 of
+// each of the 4 waves of a raster block on either side of the staged form's barrier
+// (ffmp_trace_read_waves).
 #ifdef FFMP_TRACE
 __device__ uint64_t g_trace_env[4096 * 12];
 __device__ uint64_t g_trace_ras[65536 * 4];
+__device__ uint64_t g_trace_wave[65536 * 8];
+#define FFMP_WAVE_STAMP(k)                                                                         \
+  do {                                                                                             \
+    __builtin_amdgcn_s_waitcnt(0);                                                                 \
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < 65536)                                             \
+      g_trace_wave[(blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + (k)] = wall_clock64();              \
+  } while (0)
 #define FFMP_ENV_STAMP(k)                                                   \
   do {                                                                      \
     __builtin_amdgcn_s_waitcnt(0);                                          \
@@ -204,6 +215,7 @@ __device__ uint64_t g_trace_ras[65536 * 4];
 #else
 #define FFMP_ENV_STAMP(k) do {} while (0)
 #define FFMP_RAS_STAMP(k) do {} while (0)
+#define FFMP_WAVE_STAMP(k) do {} while (0)
 #endif
 
 // One env's raster record: header, goal, then K float4 of each of cur / prev / vel.
@@ -951,7 +963,9 @@ FFMP_DEV __attribute__((always_inline)) void raster_env(const ffmp_cfg_t& cfg, i
       s_prev[tid] = make_float4(q[0], q[1], q[2], q[3]);
       if (FLOW) s_vel[tid] = make_float2(ro[4 * (2 * K + tid)], ro[4 * (2 * K + tid) + 1]);
     }
+    FFMP_WAVE_STAMP(0);
     __syncthreads();
+    FFMP_WAVE_STAMP(1);
   }
   if (!PRELOADED) FFMP_RAS_STAMP(1);
 
@@ -1356,6 +1370,7 @@ __global__ __launch_bounds__(256, (kTagWaves<TG...> ? kTagWaves<TG...> : FMT == 
   __shared__ float4 s_cur[FFMP_MAX_OBST], s_prev[FFMP_MAX_OBST];
   __shared__ float2 s_vel[FLOW ? FFMP_MAX_OBST : 1];
   __shared__ float s_hdr[FFMP_REC_HDR];
+  FFMP_RAS_STAMP(3);  // kernel entry: ahead of the block index, the mask and the old tags
   const int64_t lb = logical_block<XCD>();
   const int64_t e = lb / bpe;
   const int tile = (int)(lb - e * bpe);
@@ -1370,6 +1385,304 @@ __global__ __launch_bounds__(256, (kTagWaves<TG...> ? kTagWaves<TG...> : FMT == 
   }
   raster_env<NT, FLOW, FMT, false, TAGS, kTagWaves<TG...>>(cfg, e, tile, cells_per_block, record, state_m, sm_stride, sm_frame, newest_only,
                                          pot, flow, tile_log2r, s_cur, s_prev, s_vel, s_hdr, tc);
+#ifdef FFMP_TRACE
+  __syncthreads();
+  FFMP_RAS_STAMP(2);
+#endif
+}
+
+// FFMP_RASTER_DIRECT: the tagged float32 raster at kRasterWaves waves per SIMD (no flow planes) whose
+// blocks use no LDS and no barrier, and whose waves make one memory round trip before their first task
+// and never wait for each other.  The staged form's block start is a chain — old tags (an HBM miss, byte
+// by byte) -> header -> discs -> barrier -> header back out of LDS -> 1/G -> the band precompute — paid
+// four times per env at C3's 16,384-cell blocks.  Here every wave issues all of its loads at once:
+//   header   11 words through scalar loads (e is block-uniform, the record is the previous kernel's);
+//   discs    lane k its own disc of both frames, straight into the cull operands (16-B loads where the
+//            launch found the record 16-B aligned, 4-B loads otherwise); inside the disc loops the
+//            culled disc's operands come from the owning lane (v_readlane, the index is wave-uniform);
+//   tags     lane l the 4 old tag bytes (one per 16-lane group) of the wave's l-th task, packed into one
+//            register per slot; the task loop takes its word by v_readlane and the group its byte by a
+//            shift.  A wave has at most 64 tasks (blocks of <= kTagLdsCap granules).  A newest-only
+//            launch loads the older slot's tags only for a reset env (a second trip, rare);
+//   mask     the env's byte, tested after the one wait.
+// The host passes 1/G, the rows per block and 32-bit block counts (no 64-bit division, no IEEE
+// reciprocal).  The same float32 operations in the same order per cell as raster_env, the same store
+// decision from the same old tag, the same tag bytes from the same lanes: bit-identical planes and tags.
+// Shapes: row runs, and 2-D tiles of 2 or 4 rows in the column-band-major deal; the launch takes the
+// staged twin for every other shape.
+FFMP_DEV float lane_f(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+
+template <bool NT, bool XCD, bool REC16>
+__global__ __launch_bounds__(256, kRasterWaves) void raster_direct_kernel(
+    ffmp_cfg_t cfg, uint32_t n, uint32_t bpe, int32_t cells_per_block, int32_t rows_per_block, float invG,
+    const float* __restrict__ record, const uint8_t* __restrict__ mask, float* __restrict__ state_m,
+    int64_t sm_stride, int64_t sm_frame, int32_t newest_only, float* __restrict__ pot, int32_t tile_log2r,
+    TagArgs tg) {
+  FFMP_RAS_STAMP(3);
+  uint32_t lb = blockIdx.x;
+  if (XCD) {
+    const uint32_t per = gridDim.x / 8;
+    if (lb < per * 8) lb = (lb % 8) * per + lb / 8;
+  }
+  const uint32_t e = lb / bpe;
+  const int tile = (int)(lb - e * bpe);
+  if (e >= n) return;
+  const int K = cfg.n_obst, G = cfg.grid, G2 = G * G;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool tiled = tile_log2r > 0;
+  const int qbeg = tile * cells_per_block;
+
+  // the deal of wave tasks: row runs take tasks wave, wave + 4, ... of 256 consecutive cells; tiles
+  // take column bands cb0, cb0 + 4, ... and of each the row bands b0, b0 + wpc, ... (raster_env)
+  const int R = 1 << tile_log2r, C = 256 >> tile_log2r, lanes_per_row = 64 >> tile_log2r;
+  const int ncb = max(G >> (8 - tile_log2r), 1);  // G / C
+  const int row0 = tile * rows_per_block;
+  const int cb0 = ncb >= 4 ? wave : (wave & (ncb - 1));
+  const int b0 = ncb >= 4 ? 0 : (wave >> (ncb - 1));
+  const int wsh = ncb >= 4 ? 0 : 3 - ncb, wpc = 1 << wsh;  // waves per column band: 4 / ncb, at least 1
+
+  // ---- every load of the wave in one basic block, then one wait.  No branch from here to the task
+  // loops: a lane without a disc reads the header in its place, a launch without a mask the record's
+  // first byte, and a masked env gets empty loops, so that the compiler keeps the loads together.
+  const float* rec = record + (int64_t)e * rec_stride(K);
+  float h[11];
+#pragma unroll
+  for (int i = 0; i < 11; ++i) h[i] = rec[i];
+  const uint8_t mbyte = *(mask ? mask + e : reinterpret_cast<const uint8_t*>(rec));
+  const bool has = lane < K;
+  const float* dc = has ? rec + FFMP_REC_HDR + 4 * lane : rec;
+  const float* dp = has ? dc + 4 * K : rec;
+  float4 oc, op;
+  if constexpr (REC16) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(dc), b = *reinterpret_cast<const f32x4*>(dp);
+    oc = make_float4(a.x, a.y, a.z, a.w);
+    op = make_float4(b.x, b.y, b.z, b.w);
+  } else {  // 4-B words: the ABI asks no more alignment of the record
+    oc = make_float4(dc[0], dc[1], dc[2], dc[3]);
+    op = make_float4(dp[0], dp[1], dp[2], dp[3]);
+  }
+  uint8_t* t0 = tg.older + (int64_t)e * tg.env_stride;
+  uint8_t* t1 = tg.newest + (int64_t)e * tg.env_stride;
+  // the old tags of this wave's task `lane`: the granule of each of its four 16-lane groups (the
+  // block's first granule where the wave has no such task).  A newest-only launch reads the newest
+  // slot's bytes twice here; it needs the older slot's only for a reset env (below).
+  const int nrows = min(rows_per_block, G - row0);
+  const int nbw_all = ((nrows >> tile_log2r) - b0 + wpc - 1) >> wsh;  // row bands of this wave per column band (may be <= 0)
+  const int qend_all = min(qbeg + cells_per_block, G2);
+  const int ci = ncb > 4 ? (int)(((float)lane + 0.5f) * __builtin_amdgcn_rcpf((float)max(nbw_all, 1))) : 0;
+  const int bi = lane - ci * nbw_all;
+  const int cbl = cb0 + 4 * ci;
+  const uint8_t* tl0 = newest_only ? t1 : t0;
+  uint32_t b0v[4], b1v[4];
+  int gran[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int rg = (16 * g) >> (6 - tile_log2r);
+    const int qt = (row0 + (b0 + bi * wpc) * R + rg) * G + cbl * C + (16 * g - rg * lanes_per_row) * 4;
+    const int qr = qbeg + (wave + 4 * lane) * 256 + 64 * g;
+    const bool ok = tiled ? (cbl < ncb && bi < nbw_all) : (qr < qend_all);
+    const int gr = (ok ? (tiled ? qt : qr) : qbeg) >> 6;
+    gran[g] = gr;
+    b0v[g] = tl0[gr];
+    b1v[g] = t1[gr];
+  }
+  uint32_t w0 = b0v[0] | (b0v[1] << 8) | (b0v[2] << 16) | (b0v[3] << 24);
+  const uint32_t w1 = b1v[0] | (b1v[1] << 8) | (b1v[2] << 16) | (b1v[3] << 24);
+  const bool live = !mask || __builtin_amdgcn_readfirstlane((int)mbyte) != 0;
+  // a masked env: no tasks
+  const int nbands = live ? nrows >> tile_log2r : 0;
+  const int qend = live ? qend_all : qbeg;
+  FFMP_RAS_STAMP(1);
+  const FrameHdr hc{h[0], h[1], h[2], h[3]};
+  const FrameHdr hp{h[4], h[5], h[6], h[7]};
+  const float gx = h[8], gy = h[9];
+  // temporal stack in place: the older frame already holds the previous newest one unless this
+  // env was reset (block-uniform)
+  const bool write_old = !newest_only || h[10] != 0.0f;
+  if (newest_only && write_old) {  // a reset env under a newest-only launch: the older slot's tags after all
+#pragma unroll
+    for (int g = 0; g < 4; ++g) b0v[g] = t0[gran[g]];
+    w0 = b0v[0] | (b0v[1] << 8) | (b0v[2] << 16) | (b0v[3] << 24);
+  }
+  const float res = cfg.res_f, half = cfg.half_f;
+  const bool with_pot = pot != nullptr;
+  const float rc = oc.w + (with_pot ? cfg.rho0_f : 0.0f) + cfg.cull_margin_f;
+  const float rp = op.w + cfg.cull_margin_f;
+  const float rc2 = rc * rc, rp2 = rp * rp;
+  const FrameHdr hq = (lane < 4) ? hc : hp;
+  float* m0 = state_m + (int64_t)e * sm_stride;
+  float* m1 = m0 + sm_frame;
+  float* pp = pot ? pot + (int64_t)e * G2 : nullptr;
+  const int bsh = (lane >> 4) * 8;  // this lane's group's byte of a task's tag word
+
+  // does this lane's 16-lane group (one granule, at plane offset q) store its frame words?  Writes the
+  // granule's tag (raster_env's tag_gate with the old tag out of the task's word)
+  auto tag_gate = [&](bool nzlane, uint8_t* t, uint32_t word, int q) -> bool {
+    const bool nz = ((__ballot(nzlane) >> (lane & 48)) & 0xFFFFull) != 0ull;
+    const bool old = ((word >> bsh) & 0xFFu) != 0u;
+    if ((lane & 15) == 0) t[q >> 6] = nz ? 1 : 0;
+    return nz || old;
+  };
+
+  if (tile_log2r > 0) {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const int r = lane >> (6 - tile_log2r);
+    const int cl = (lane - r * lanes_per_row) * 4;
+    const f2 hka = {cfg.half_ka_f, cfg.half_ka_f};
+    int t = 0;
+    for (int cb = cb0; cb < ncb; cb += 4) {
+      const int jb = cb * C, j = jb + cl;
+      const float by0 = (float)jb * res - half, by1 = (float)(jb + C - 1) * res - half;
+      const float dyc = fmaxf(fmaxf(by0 - oc.y, oc.y - by1), 0.0f);
+      const float dyp = fmaxf(fmaxf(by0 - op.y, op.y - by1), 0.0f);
+      const float tc = rc2 - dyc * dyc, tp = rp2 - dyp * dyp;
+      f2 ey2[2], dyy2[2];
+#pragma unroll
+      for (int p2 = 0; p2 < 2; ++p2) {
+        ey2[p2] = f2{(float)(j + 2 * p2) * res - half, (float)(j + 2 * p2 + 1) * res - half};
+        const f2 dy = ey2[p2] - gy;
+        dyy2[p2] = dy * dy;
+      }
+      for (int band = b0; band < nbands; band += wpc, ++t) {
+        const int i0 = row0 + band * R;
+        const int i = i0 + r;
+        const int q = i * G + j;
+        const float bx0 = (float)i0 * res - half, bx1 = (float)(i0 + R - 1) * res - half;
+        const float dxc = fmaxf(fmaxf(bx0 - oc.x, oc.x - bx1), 0.0f);
+        const uint64_t mc = __ballot(has && dxc * dxc <= tc);
+        uint64_t mp = 0ull;
+        if (write_old) {
+          const float dxp = fmaxf(fmaxf(bx0 - op.x, op.x - bx1), 0.0f);
+          mp = __ballot(has && dxp * dxp <= tp);
+        }
+        const uint64_t wb = __ballot(lane >= 8 || corner_inside(cfg, hq, (lane & 1) ? bx1 : bx0,
+                                                                 (lane & 2) ? by1 : by0));
+        const bool walls_c = (wb & 0xFull) != 0xFull;
+        const bool walls_p = write_old && (wb & 0xF0ull) != 0xF0ull;
+        const float ex = (float)i * res - half;
+        uint32_t wc = 0u, wp = 0u;
+        f2 U2[2];
+        if (with_pot) {
+          const float dx = ex - gx;
+          const f2 dxx = {dx * dx, dx * dx};
+#pragma unroll
+          for (int p2 = 0; p2 < 2; ++p2) U2[p2] = hka * (dxx + dyy2[p2]);
+        }
+        if (walls_c) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (outside_world(cfg, hc, ex, ey2[u >> 1][u & 1])) wc |= 0xFFu << (8 * u);
+        }
+        if (walls_p) {
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (outside_world(cfg, hp, ex, ey2[u >> 1][u & 1])) wp |= 0xFFu << (8 * u);
+        }
+        for (uint64_t m = mp; m; m &= m - 1) {
+          const int k = __builtin_ctzll(m);
+          const float4 o = make_float4(lane_f(op.x, k), lane_f(op.y, k), lane_f(op.z, k), 0.0f);
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (in_disc(ex, ey2[u >> 1][u & 1], o)) wp |= 0xFFu << (8 * u);
+        }
+        for (uint64_t m = mc; m; m &= m - 1) {
+          const int k = __builtin_ctzll(m);
+          const float4 o = make_float4(lane_f(oc.x, k), lane_f(oc.y, k), lane_f(oc.z, k), lane_f(oc.w, k));
+          const float reach2 = rep_reach2(cfg, o.w);
+          const float dx = ex - o.x;
+          const f2 dxx = {dx * dx, dx * dx};
+#pragma unroll
+          for (int p2 = 0; p2 < 2; ++p2) {
+            const f2 dy = ey2[p2] - o.y;
+            const f2 d2 = dxx + dy * dy;  // in_disc's and add_repulsive's operand
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              const int u = 2 * p2 + c;
+              if (d2[c] <= o.z) wc |= 0xFFu << (8 * u);
+              if (with_pot) U2[p2][c] = add_repulsive_s(cfg, U2[p2][c], d2[c], o.w, reach2);
+            }
+          }
+        }
+        // byte 0xFF -> 255.0f, 0 -> 0.0f: the reference layout's occ * 255 values
+        bool st_p = true;
+        if (write_old) st_p = tag_gate(wp != 0u, t0, (uint32_t)__builtin_amdgcn_readlane((int)w0, t), q);
+        const bool st_c = tag_gate(wc != 0u, t1, (uint32_t)__builtin_amdgcn_readlane((int)w1, t), q);
+        if (write_old && st_p)
+          store4<NT>(m0 + q, (float)(wp & 0xFFu), (float)((wp >> 8) & 0xFFu), (float)((wp >> 16) & 0xFFu),
+                     (float)(wp >> 24));
+        if (st_c)
+          store4<NT>(m1 + q, (float)(wc & 0xFFu), (float)((wc >> 8) & 0xFFu), (float)((wc >> 16) & 0xFFu),
+                     (float)(wc >> 24));
+        if (pp) store4<NT>(pp + q, U2[0].x, U2[0].y, U2[1].x, U2[1].y);
+      }
+    }
+  } else {
+    int t = 0;
+    for (int q0 = qbeg + wave * 256; q0 < qend; q0 += 1024, ++t) {
+      // ---- wave chunk [q0, qlast] (256 consecutive cells) -> ego bounding box ----
+      const int qlast = min(q0 + 255, G2 - 1);
+      const int i0 = q0 / G;
+      const int r0 = q0 - i0 * G;
+      const int i1 = i0 + small_div(r0 + (qlast - q0), invG);
+      int j0 = 0, j1 = G - 1;
+      if (i0 == i1) { j0 = r0; j1 = r0 + (qlast - q0); }
+      const int off = r0 + lane * 4;
+      const int q = q0 + lane * 4;
+      const int di = small_div(off, invG);
+      const int i = i0 + di, j = off - di * G;
+      const float bx0 = (float)i0 * res - half, bx1 = (float)i1 * res - half;
+      const float by0 = (float)j0 * res - half, by1 = (float)j1 * res - half;
+      // ---- lane-parallel cull ----
+      const uint64_t mc = __ballot(has && box_dist2(oc.x, oc.y, bx0, bx1, by0, by1) <= rc2);
+      const uint64_t mp = write_old ? __ballot(has && box_dist2(op.x, op.y, bx0, bx1, by0, by1) <= rp2) : 0ull;
+      const uint64_t wb = __ballot(lane >= 8 || corner_inside(cfg, hq, (lane & 1) ? bx1 : bx0,
+                                                               (lane & 2) ? by1 : by0));
+      const bool walls_c = (wb & 0xFull) != 0xFull;
+      const bool walls_p = write_old && (wb & 0xF0ull) != 0xF0ull;
+      const uint32_t tw0 = (uint32_t)__builtin_amdgcn_readlane((int)w0, t);
+      const uint32_t tw1 = (uint32_t)__builtin_amdgcn_readlane((int)w1, t);
+      if (q < qend) {
+        // ---- this lane's 4 cells ----
+        const float ex = (float)i * res - half;
+        float ey[4], occp[4], occc[4], U[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) ey[u] = (float)(j + u) * res - half;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          occp[u] = (walls_p && outside_world(cfg, hp, ex, ey[u])) ? 1.0f : 0.0f;
+          occc[u] = (walls_c && outside_world(cfg, hc, ex, ey[u])) ? 1.0f : 0.0f;
+          U[u] = with_pot ? attractive(cfg, ex, ey[u], gx, gy) : 0.0f;
+        }
+        for (uint64_t m = mp; m; m &= m - 1) {
+          const int k = __builtin_ctzll(m);
+          const float4 o = make_float4(lane_f(op.x, k), lane_f(op.y, k), lane_f(op.z, k), 0.0f);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) if (in_disc(ex, ey[u], o)) occp[u] = 1.0f;
+        }
+        for (uint64_t m = mc; m; m &= m - 1) {
+          const int k = __builtin_ctzll(m);
+          const float4 o = make_float4(lane_f(oc.x, k), lane_f(oc.y, k), lane_f(oc.z, k), lane_f(oc.w, k));
+          const float reach2 = rep_reach2(cfg, o.w);
+          const float dx = ex - o.x;
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float dy = ey[u] - o.y;
+            const float d2 = dx * dx + dy * dy;  // in_disc's and add_repulsive's operand
+            if (d2 <= o.z) occc[u] = 1.0f;
+            if (with_pot) U[u] = add_repulsive_s(cfg, U[u], d2, o.w, reach2);
+          }
+        }
+        bool st_p = true;
+        if (write_old) st_p = tag_gate((occp[0] + occp[1]) + (occp[2] + occp[3]) != 0.0f, t0, tw0, q);
+        const bool st_c = tag_gate((occc[0] + occc[1]) + (occc[2] + occc[3]) != 0.0f, t1, tw1, q);
+        if (write_old && st_p)
+          store4<NT>(m0 + q, occp[0] * 255.0f, occp[1] * 255.0f, occp[2] * 255.0f, occp[3] * 255.0f);
+        if (st_c) store4<NT>(m1 + q, occc[0] * 255.0f, occc[1] * 255.0f, occc[2] * 255.0f, occc[3] * 255.0f);
+        if (pp) store4<NT>(pp + q, U[0], U[1], U[2], U[3]);
+      }
+    }
+  }
 #ifdef FFMP_TRACE
   __syncthreads();
   FFMP_RAS_STAMP(2);
@@ -1920,6 +2233,35 @@ int raster_waves(int32_t flags, bool tagged, bool ct, bool flow) {
   return (flags & FFMP_RASTER_WAVES) ? kRasterWaves : 0;
 }
 
+// FFMP_RASTER_DIRECT -> does ffmp_raster_ex launch raster_direct_kernel?  Where FFMP_RASTER_WAVES would select
+// the tagged float32 kernel (tags, float32 frames, no flow planes), for row runs and 2- / 4-row tiles in the
+// column-band-major deal (tile_log2r as the launch settled it), in blocks whose old tags the staged form
+// would stage too.  Elsewhere the flag is ignored.
+bool raster_direct(int32_t flags, bool tagged, bool ct, bool flow, int grid, int cpb, int32_t tile_log2r) {
+  if (!(flags & FFMP_RASTER_DIRECT) || !tagged || ct || flow || tile_log2r > 2) return false;
+  const int G2 = grid * grid;
+  if (((cpb < G2 ? cpb : G2) + 63) / 64 > kTagLdsCap) return false;
+  if (tile_log2r == 0) return true;
+  const int ncb = grid / (256 >> tile_log2r);
+  return ncb > 0 && ((4 % ncb) == 0 || (ncb % 4) == 0);
+}
+
+// The launch shape of ffmp_raster_ex: cells per block, and the 2-D wave tiles (R rows x (cells per wave
+// task)/R columns) where the plane and the block split into them, else 0: the 1-D chunks.
+void raster_shape(int grid, int32_t cells_per_block, int fmt, int32_t flags, int* cpb_out, int32_t* tile_log2r_out) {
+  const int G2 = grid * grid;
+  const int cpb_max = cells_per_block ? cells_per_block : 4096;
+  const int cpb = G2 < cpb_max ? ((G2 + 1023) / 1024) * 1024 : cpb_max;
+  int32_t tile_log2r = tile_rows_log2(flags);
+  if (tile_log2r) {
+    const int C = (fmt == FMT_CT16 ? 1024 : fmt == FMT_CT8 ? 512 : 256) >> tile_log2r, R = 1 << tile_log2r;
+    const bool whole_bands = cpb >= G2 || (cpb % (grid * R)) == 0;
+    if ((grid % C) != 0 || !whole_bands) tile_log2r = 0;  // the 1-D chunks (identical results)
+  }
+  *cpb_out = cpb;
+  *tile_log2r_out = tile_log2r;
+}
+
 // The granule tags behind an ffmp_obs_t with FFMP_OBS_EXT_TAGS (include/ffmp.h ffmp_obs_tags_t), checked;
 // *on = false without the flag.
 int obs_tags(const ffmp_cfg_t* cfg, const ffmp_obs_t* o, TagArgs* t, bool* on) {
@@ -2225,8 +2567,11 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
   if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
   if (n == 0) return FFMP_OK;
   const int G2 = cfg->grid * cfg->grid;
-  const int cpb_max = cells_per_block ? cells_per_block : 4096;
-  const int cpb = G2 < cpb_max ? ((G2 + 1023) / 1024) * 1024 : cpb_max;
+  const bool ct = obs->format == FFMP_OBS_U8F16;
+  const int fmt = raster_format(ct, cfg->grid, flags);
+  int cpb = 0;
+  int32_t tile_log2r = 0;
+  raster_shape(cfg->grid, cells_per_block, fmt, flags, &cpb, &tile_log2r);
   const int bpe = (G2 + cpb - 1) / cpb;
   // a launch holds at most 2^31 - 1 work-items: larger batches go out as several launches over
   // consecutive env ranges (the whole C5 workload in the compact format is 131,072 x 64 blocks)
@@ -2236,7 +2581,6 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
   const bool xcd = (flags & FFMP_RASTER_XCD) != 0;
   const bool fl = cfg->flow != 0;
   if (fl && !obs->flow) return fail(FFMP_E_ARG, "cfg.flow is set but obs.flow is NULL");
-  const bool ct = obs->format == FFMP_OBS_U8F16;
   const int64_t sm_stride = obs->state_m_stride ? obs->state_m_stride : 2 * (int64_t)G2;
   const int64_t sm_frame = obs->state_m_frame_stride ? obs->state_m_frame_stride : (int64_t)G2;
   const int64_t sm_frame_abs = sm_frame < 0 ? -sm_frame : sm_frame;  // negative: newest in a lower slot
@@ -2245,16 +2589,8 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
     return fail(FFMP_E_ARG, "state_m strides overlap: env %lld, frame %lld elements (G*G = %d)",
                 (long long)sm_stride, (long long)sm_frame, G2);
   const int32_t newest = (flags & FFMP_RASTER_NEWEST) ? 1 : 0;
-  // 2-D wave tiles: R rows x 256/R columns, where the plane and the block split into them
-  const int fmt = raster_format(ct, cfg->grid, flags);
   const int waves = raster_waves(flags, tagged, ct, fl);
-  // 2-D wave tiles: R rows x (cells per wave task)/R columns, where the plane and the block split into them
-  int32_t tile_log2r = tile_rows_log2(flags);
-  if (tile_log2r) {
-    const int C = (fmt == FMT_CT16 ? 1024 : fmt == FMT_CT8 ? 512 : 256) >> tile_log2r, R = 1 << tile_log2r;
-    const bool whole_bands = cpb >= G2 || (cpb % (cfg->grid * R)) == 0;
-    if ((cfg->grid % C) != 0 || !whole_bands) tile_log2r = 0;  // the 1-D chunks (identical results)
-  }
+  const bool direct = raster_direct(flags, tagged, ct, fl, cfg->grid, cpb, tile_log2r);
   const dim3 block(256);
   hipStream_t s = (hipStream_t)stream;
   const int64_t rs = rec_stride(cfg->n_obst);
@@ -2276,6 +2612,20 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
                                pot, flw, tile_log2r, t);
           };
           if constexpr (!decltype(FL_)::value) {
+            if (direct) {
+              // per launch, once: 1 / G as the kernels compute it, the rows of a block (tiles: whole
+              // bands), and whether lane k's discs may be read as 16-B words
+              const int32_t rpb = (cpb < G2 ? cpb : G2) / cfg->grid;
+              auto go = [&](auto R16_) {
+                hipLaunchKernelGGL((raster_direct_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(R16_)::value>),
+                                   grid, block, tuning().lds_pad, s, *cfg, (uint32_t)m, (uint32_t)bpe, cpb, rpb,
+                                   1.0f / (float)cfg->grid, rec, msk, sm, sm_stride, sm_frame, newest, pot, tile_log2r, tg);
+              };
+              // every env's record is 64 + 48 K bytes: 16-B aligned with the first
+              if ((reinterpret_cast<uintptr_t>(rec) & 15u) == 0) go(std::true_type{});
+              else go(std::false_type{});
+              return;
+            }
             if (waves == kRasterWaves) return launch(TagArgsW<kRasterWaves>{tg});
           }
           launch(tg);
@@ -2538,6 +2888,23 @@ int ffmp_raster_waves(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t flag
   return raster_waves(flags, tagged, obs->format == FFMP_OBS_U8F16, cfg->flow != 0);
 }
 
+int ffmp_raster_direct(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t cells_per_block, int32_t flags) {
+  int rc = check_cfg(cfg);
+  if (rc) return rc;
+  if (!obs) return fail(FFMP_E_ARG, "obs is NULL");
+  if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
+  TagArgs tags{};
+  bool tagged = false;
+  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
+  const bool ct = obs->format == FFMP_OBS_U8F16;
+  if (cells_per_block != 0 && (cells_per_block < 1024 || cells_per_block % 1024 != 0))
+    return fail(FFMP_E_ARG, "cells_per_block must be 0 or a multiple of 1024, got %d", cells_per_block);
+  int cpb = 0;
+  int32_t tile_log2r = 0;
+  raster_shape(cfg->grid, cells_per_block, raster_format(ct, cfg->grid, flags), flags, &cpb, &tile_log2r);
+  return raster_direct(flags, tagged, ct, cfg->flow != 0, cfg->grid, cpb, tile_log2r) ? 1 : 0;
+}
+
 int ffmp_step_skewed_check(const ffmp_cfg_t* cfg, int32_t format, int32_t flags) {
   int rc = check_cfg(cfg);
   if (rc) return rc;
@@ -2795,6 +3162,16 @@ int ffmp_trace_read(uint64_t* env_host, uint64_t* ras_host, int clear) {
       return fail(FFMP_E_HIP, "ffmp_trace_read: clear failed");
   }
   return hipDeviceSynchronize() == hipSuccess ? FFMP_OK : fail(FFMP_E_HIP, "ffmp_trace_read: sync failed");
+}
+// Probe builds only: the per-wave barrier stamps (65536 blocks x 4 waves x 2 uint64) to host memory.
+int ffmp_trace_read_waves(uint64_t* wave_host, int clear) {
+  if (hipMemcpyFromSymbol(wave_host, HIP_SYMBOL(g_trace_wave), sizeof(uint64_t) * 65536 * 8) != hipSuccess)
+    return fail(FFMP_E_HIP, "ffmp_trace_read_waves: copy failed");
+  void* p = nullptr;
+  if (clear && (hipGetSymbolAddress(&p, HIP_SYMBOL(g_trace_wave)) != hipSuccess ||
+                hipMemset(p, 0, sizeof(uint64_t) * 65536 * 8) != hipSuccess))
+    return fail(FFMP_E_HIP, "ffmp_trace_read_waves: clear failed");
+  return hipDeviceSynchronize() == hipSuccess ? FFMP_OK : fail(FFMP_E_HIP, "ffmp_trace_read_waves: sync failed");
 }
 #endif
 }  // extern "C"

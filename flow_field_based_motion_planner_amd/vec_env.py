@@ -594,6 +594,23 @@ class FFMPVec:
         (4096, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4 | _abi.RASTER_WAVES),
         (8192, _abi.RASTER_NT | _abi.RASTER_TILE4 | _abi.RASTER_WAVES),
         (16384, _abi.RASTER_NT | _abi.RASTER_TILE2 | _abi.RASTER_WAVES), (4096, _abi.RASTER_NT | _abi.RASTER_WAVES),
+        # 16,384-cell tiled blocks with the XCD remap, plain and held to 6 waves per SIMD: at C3 with tags the
+        # 4-row tiles run 1.51-1.53 ms per newest-only launch against 1.57-1.59 without the remap
+        # (profiles/raster_direct_variants.json)
+        (16384, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4), (16384, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE2),
+        (16384, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4 | _abi.RASTER_WAVES),
+        (16384, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE2 | _abi.RASTER_WAVES),
+    )
+
+    # Granule tags only, the two-launch raster: the tagged kernel at 6 waves per SIMD whose blocks use no
+    # LDS and no barrier and make one memory round trip (RASTER_DIRECT), beside each of its staged twins
+    # above.  A list of its own: the flag stands without RASTER_WAVES, and the one-launch step ignores it.
+    DIRECT_SHAPES = (
+        (4096, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4 | _abi.RASTER_DIRECT),
+        (8192, _abi.RASTER_NT | _abi.RASTER_TILE4 | _abi.RASTER_DIRECT),
+        (16384, _abi.RASTER_NT | _abi.RASTER_TILE2 | _abi.RASTER_DIRECT), (4096, _abi.RASTER_NT | _abi.RASTER_DIRECT),
+        (16384, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE4 | _abi.RASTER_DIRECT),
+        (16384, _abi.RASTER_NT | _abi.RASTER_XCD | _abi.RASTER_TILE2 | _abi.RASTER_DIRECT),
     )
 
     def _raster_gbs_steady(self, steps: int = 3) -> Dict[bool, Tuple[float, float]]:
@@ -965,19 +982,20 @@ class FFMPVec:
     # leave tag 1 behind, which would also make the next candidate's first ring cycle dense: dropped.
     # The RASTER_WAVES forms select a kernel of their own only with tags (float32 frames, no flow
     # planes); elsewhere the library ignores the flag, so they would time a candidate twice: dropped.
+    # RASTER_DIRECT likewise, and only in the two-launch raster (the one-launch step ignores it).
     def _offered(self, flags: int) -> bool:
         tags = self.frame_tags is not None
-        if flags & _abi.RASTER_WAVES and not (tags and self.obs_format == "f32" and not self.cfg.flow):
+        if flags & (_abi.RASTER_WAVES | _abi.RASTER_DIRECT) and not (tags and self.obs_format == "f32" and not self.cfg.flow):
             return False
         return (self.XCD_SHAPES or not flags & _abi.RASTER_XCD) and not (tags and flags & _abi.RASTER_TILE8)
 
     def _shape_candidates(self):
-        shapes = self.COMPACT_SHAPES if self.obs_format == "u8f16" else self.RASTER_SHAPES
+        shapes = self.COMPACT_SHAPES if self.obs_format == "u8f16" else self.RASTER_SHAPES + self.DIRECT_SHAPES
         return [sh for sh in shapes if self._offered(sh[1])]
 
     def _fused_candidates(self):
         flags = self.COMPACT_FUSED_FLAGS if self.obs_format == "u8f16" else self.FUSED_FLAGS
-        return [f for f in flags if self._offered(f)]
+        return [f for f in flags if self._offered(f) and not f & _abi.RASTER_DIRECT]
 
     def _warm_tags(self) -> None:
         """One untimed ring cycle of real steps, so that every slot a timed step overwrites holds a

@@ -365,6 +365,14 @@ int ffmp_raster(const ffmp_cfg_t* cfg, int64_t n, const float* record,
                                   the 4 its registers allow.  Identical results.  Ignored without tags,
                                   in the compact format, with flow planes and by ffmp_step_skewed
                                   (ffmp_raster_waves tells). */
+#define FFMP_RASTER_DIRECT 2048 /* ffmp_raster_ex, float32 frames with granule tags, no flow planes: the tagged
+                                   kernel at 6 waves per SIMD (as FFMP_RASTER_WAVES) in the form whose blocks
+                                   use no LDS and no barrier and whose waves make one memory round trip (header
+                                   by scalar loads, each lane its own disc, each wave the old tags of its own
+                                   tasks).  Row runs, TILE2 and TILE4 in blocks of at most 65,536 cells.
+                                   Identical results and tag bytes.  Ignored wherever FFMP_RASTER_WAVES is, with
+                                   TILE8 / TILE16, in larger blocks and by the one-launch and skewed steps: the
+                                   launch is then the one without the flag (ffmp_raster_direct tells). */
 int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record,
                    const uint8_t* mask, ffmp_obs_t* obs, int32_t cells_per_block,
                    int32_t flags, void* stream);
@@ -403,6 +411,11 @@ int ffmp_step_skewed_check(const ffmp_cfg_t* cfg, int32_t format, int32_t flags)
  * and of the tag extension and their own decision, reads no device memory and launches nothing.  Negative:
  * FFMP_E_ARG with the reason in ffmp_last_error(). */
 int ffmp_raster_waves(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t flags);
+
+/* Would ffmp_raster_ex with these cells_per_block and flags on this obs launch the FFMP_RASTER_DIRECT form?
+ * 1: yes, 0: its staged twin or the plain kernel (ffmp_raster_waves tells which).  The launch's own
+ * checks and decision; reads no device memory and launches nothing.  Negative: FFMP_E_ARG. */
+int ffmp_raster_direct(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t cells_per_block, int32_t flags);
 
 /* A scripted reactive controller — no reference counterpart (the reference's actions come from its
  * Q-network, src/train.py:336-347, published as /cmd_vel :665-682) — for closed-loop runs in which
