@@ -6,7 +6,7 @@ LIB = flow_field_based_motion_planner_amd/lib/libffmp.so
 CSRC = flow_field_based_motion_planner_amd/csrc
 SRC = $(CSRC)/ffmp_kernels.hip $(CSRC)/ffmp_ring.hip $(CSRC)/ffmp_conv.hip $(CSRC)/ffmp_nav.hip \
       $(CSRC)/ffmp_visible.hip $(CSRC)/ffmp_scan.hip $(CSRC)/ffmp_flowest.hip $(CSRC)/ffmp_predict.hip
-HDRS = $(CSRC)/ffmp_device.h include/ffmp.h
+HDRS = $(CSRC)/ffmp_device.h $(CSRC)/ffmp_host.h $(CSRC)/ffmp_raster_plan.h include/ffmp.h
 OBJDIR = build/obj
 OBJ = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRC))
 
@@ -27,10 +27,11 @@ probe: $(SRC) $(HDRS)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -shared -o tools/_probe/libffmp_$(V).so $(SRC)
 
 # the same with only the convolutions rebuilt (the other objects as `make` built them)
-probe-conv: $(OBJDIR)/ffmp_kernels.o $(OBJDIR)/ffmp_ring.o $(OBJDIR)/ffmp_nav.o $(CSRC)/ffmp_conv.hip $(HDRS)
+OBJ_NOCONV = $(filter-out $(OBJDIR)/ffmp_conv.o,$(OBJ))
+probe-conv: $(OBJ_NOCONV) $(CSRC)/ffmp_conv.hip $(HDRS)
 	@mkdir -p tools/_probe
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -c -o build/conv_$(V).o $(CSRC)/ffmp_conv.hip
-	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o tools/_probe/libffmp_$(V).so $(OBJDIR)/ffmp_kernels.o $(OBJDIR)/ffmp_ring.o $(OBJDIR)/ffmp_nav.o build/conv_$(V).o
+	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o tools/_probe/libffmp_$(V).so $(OBJ_NOCONV) build/conv_$(V).o
 
 asm: $(SRC) $(HDRS)
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Iinclude -S --cuda-device-only -o /tmp/ffmp_kernels.s $(CSRC)/ffmp_kernels.hip

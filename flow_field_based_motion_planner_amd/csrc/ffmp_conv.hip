@@ -31,10 +31,9 @@
 #include <mutex>
 #include <utility>
 
-#include "ffmp.h"
+#include "ffmp_host.h"
 
 namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
 // ffmp_conv2d_check: run every shape check of a launch, then return before launching
 thread_local bool t_conv_dry = false;
 // the MFMA shape of the convolution kernels that have both (FFMP_TUNE_CONV_MFMA): 0 = each kernel's
@@ -112,7 +111,6 @@ int conv_kys_swap(int v) {
   return prev;
 }
 }
-using ffmp_detail::fail;
 using ffmp_detail::t_conv_dry;
 
 namespace {

@@ -35,13 +35,9 @@
 #include <atomic>
 
 #include "ffmp_device.h"
+#include "ffmp_host.h"
 
 #pragma clang fp contract(off)
-
-namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
-}
-using ffmp_detail::fail;
 
 namespace {
 
@@ -430,9 +426,7 @@ int ffmp_scan_flow(const ffmp_cfg_t* cfg, int64_t n, const uint8_t* cur, const u
     }
   }
   hipLaunchKernelGGL(k, dim3((unsigned)n), dim3(kFlowThreads), lds, (hipStream_t)stream, *cfg, a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok(who);
 }
 
 }  // extern "C"

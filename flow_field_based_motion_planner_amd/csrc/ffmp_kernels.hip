@@ -10,8 +10,12 @@
 //                      writes the two float32 occupancy frames of state_m and
 //                      the float32 potential plane with 16-B stores; obstacles
 //                      staged in LDS and culled per 256-cell wave chunk.
+//   raster_direct_kernel the tagged float32 raster without LDS or barrier (FFMP_RASTER_DIRECT): every
+//                      wave reads its record and its old tags itself.
 //   step_raster_kernel the one-launch step: one block per env, env step then raster.
+//   skew_kernel        the skewed step: the env step of t + 1 in the raster launch of t.
 //   reward_done_kernel / footprint_kernel / scan_kernel — legacy FFMP methods.
+// How a raster is launched (format, block, tiles, tagged form) is decided in ffmp_raster_plan.h.
 // The seamless frame ring (HIP virtual memory) and the DLPack hand-off: ffmp_ring.hip.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -25,46 +29,33 @@
 #include <string.h>
 
 #include "ffmp_device.h"
+#include "ffmp_host.h"
+#include "ffmp_raster_plan.h"
 
 #pragma clang fp contract(off)
 
 using namespace ffmp;
 
-// The thread-local error message behind ffmp_last_error(), shared with ffmp_ring.hip.
+// The thread-local error message behind ffmp_last_error() (ffmp_host.h).
 namespace ffmp_detail {
 thread_local char g_err[512] = "";
 
-__attribute__((format(printf, 2, 3))) int fail(int code, const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-int32_t ring_extra_swap(int32_t v);  // ffmp_ring.hip (FFMP_TUNE_RING_EXTRA)
-int conv_mfma_swap(int v);           // ffmp_conv.hip (FFMP_TUNE_CONV_MFMA)
-int conv_kys_swap(int v);            // ffmp_conv.hip (FFMP_TUNE_CONV_KYS)
-int conv_lb_swap(int v);             // ffmp_conv.hip (FFMP_TUNE_CONV_LB)
-int conv_wgpf_swap(int v);           // ffmp_conv.hip (FFMP_TUNE_CONV_WGPF)
-int conv_ba2_swap(int v);            // ffmp_conv.hip (FFMP_TUNE_CONV_BA2)
-int conv_mbw_swap(int v);            // ffmp_conv.hip (FFMP_TUNE_CONV_MBW)
-int conv_planar_swap(int v);         // ffmp_conv.hip (FFMP_TUNE_CONV_PLANAR)
-int conv_pin_swap(int v);            // ffmp_conv.hip (FFMP_TUNE_CONV_PIN)
-int conv_wgdma_swap(int v);          // ffmp_conv.hip (FFMP_TUNE_CONV_WGDMA)
+
+int launch_ok(const char* who) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? FFMP_OK : fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(e));
+}
 }  // namespace ffmp_detail
-using ffmp_detail::fail;
 using ffmp_detail::g_err;
 
 namespace {
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: HIP launch failed: %s", what, hipGetErrorString(e));
-    return FFMP_E_HIP;
-  }
-  return FFMP_OK;
-}
 
 int check_cfg(const ffmp_cfg_t* c) {
   if (!c) return fail(FFMP_E_ARG, "cfg is NULL");
@@ -108,12 +99,6 @@ int check_cfg(const ffmp_cfg_t* c) {
     if (i < 0 || j < 0 || i >= c->grid || j >= c->grid)
       return fail(FFMP_E_CFG, "footprint cell outside the grid (index %d)", f);
   }
-  return FFMP_OK;
-}
-
-int check_format(const ffmp_obs_t* o, bool flow) {
-  if (o->format != FFMP_OBS_F32 && o->format != FFMP_OBS_U8F16)
-    return fail(FFMP_E_ARG, "unknown obs.format %d", o->format);
   return FFMP_OK;
 }
 
@@ -847,13 +832,7 @@ FFMP_DEV int64_t logical_block() {
 }
 
 
-// Observation format of a raster instantiation: FMT_F32 (reference layout), FMT_CT4 (compact
-// FFMP_OBS_U8F16, 4 cells per lane) or FMT_CT16 (compact, 16 cells per lane: a wave task is
-// 1024 cells, so the per-task cull / wall / index work is spread over 4x the cells — the compact
-// raster writes 3 bytes per cell and is bound by that per-task work, not by HBM; needs G % 16 == 0).
-// FMT_CT8 (FFMP_RASTER_MID8, G % 8 == 0): 8 cells per lane, an 8-B frame store and a 16-B potential
-// store per lane (512-cell wave tasks).
-constexpr int FMT_F32 = 0, FMT_CT4 = 1, FMT_CT16 = 2, FMT_CT8 = 3;
+// The observation formats FMT_* of a raster instantiation: ffmp_raster_plan.h.
 // The CT8 raster is held to 6 waves per SIMD (84 VGPRs instead of the compiler's 112 at 4): C3
 // newest-only raster 0.985-1.025 -> 0.954-0.956 ms (profiles/r03b_ct8_shapes.txt).
 #ifndef FFMP_CT8_MIN_WAVES
@@ -873,7 +852,6 @@ constexpr int FMT_F32 = 0, FMT_CT4 = 1, FMT_CT16 = 2, FMT_CT8 = 3;
 // whole multiples of 1024 cells, so no two blocks share a tag byte.
 // Shapes whose 16-lane groups are not granules (TILE8 / TILE16 row segments of 32 / 16 cells) and
 // blocks of more than kTagLdsCap granules store everything and write tag 1 (skip == false).
-constexpr int kTagLdsCap = 1024;  // granules of one slot a block stages (a whole 256 x 256 plane)
 struct TagArgs {
   uint8_t* older;      // tags of the slot of state_m[:, 0], env 0
   uint8_t* newest;     // tags of the slot of state_m[:, 1], env 0
@@ -889,7 +867,6 @@ struct TagLds {
 // VGPRs only four waves per SIMD cover each other.  At 6 the kernels take 76 VGPRs and no scratch.
 // Asking for 5 compiles to the same 76-77 VGPRs and 6 waves, 7 keeps 12 B per lane of scratch in the
 // one-launch step for the same time, 8 spills in the band loop (profiles/fused_waves_variants.json).
-constexpr int kRasterWaves = 6;
 template <int W>
 struct TagArgsW : TagArgs {};
 template <class... TG>
@@ -1935,7 +1912,7 @@ int scan_impl(int64_t n, int32_t L, const T* ranges, double thr, uint8_t* collid
   if (n == 0) return FFMP_OK;
   hipLaunchKernelGGL(scan_kernel<T>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, n, L,
                      ranges, thr, collide, min_r);
-  return check_launch("ffmp_scan_collision");
+  return launch_ok("ffmp_scan_collision");
 }
 
 
@@ -2211,72 +2188,41 @@ __global__ __launch_bounds__(256) void bev_image_kernel(int64_t n, const void* _
 // ============================================================================
 namespace {
 
-// log2 of the rows of a 2-D wave tile (FFMP_RASTER_TILE*), 0 = 1-D chunks
-int32_t tile_rows_log2(int32_t flags) {
-  return (flags & FFMP_RASTER_TILE16) ? 4 : (flags & FFMP_RASTER_TILE8) ? 3 : (flags & FFMP_RASTER_TILE4) ? 2
-       : (flags & FFMP_RASTER_TILE2) ? 1 : 0;
-}
-
-// The raster instantiation for an obs format: compact planes use 16 cells per lane when every
-// lane's 16 cells stay in one row (G % 16 == 0) unless FFMP_RASTER_NARROW asks for 4.
-int raster_format(bool compact, int grid, int32_t flags) {
-  if (!compact) return FMT_F32;
-  if (flags & FFMP_RASTER_NARROW) return FMT_CT4;
-  if ((flags & FFMP_RASTER_MID8) && grid % 8 == 0) return FMT_CT8;
-  return grid % 16 == 0 ? FMT_CT16 : FMT_CT4;
-}
-
-// FFMP_RASTER_WAVES -> the W of the tagged float32 kernel to launch (0: the plain one).  Without tags, in
-// the compact format or with flow planes the flag is ignored.
-int raster_waves(int32_t flags, bool tagged, bool ct, bool flow) {
-  if (!tagged || ct || flow) return 0;
-  return (flags & FFMP_RASTER_WAVES) ? kRasterWaves : 0;
-}
-
-// FFMP_RASTER_DIRECT -> does ffmp_raster_ex launch raster_direct_kernel?  Where FFMP_RASTER_WAVES would select
-// the tagged float32 kernel (tags, float32 frames, no flow planes), for row runs and 2- / 4-row tiles in the
-// column-band-major deal (tile_log2r as the launch settled it), in blocks whose old tags the staged form
-// would stage too.  Elsewhere the flag is ignored.
-bool raster_direct(int32_t flags, bool tagged, bool ct, bool flow, int grid, int cpb, int32_t tile_log2r) {
-  if (!(flags & FFMP_RASTER_DIRECT) || !tagged || ct || flow || tile_log2r > 2) return false;
-  const int G2 = grid * grid;
-  if (((cpb < G2 ? cpb : G2) + 63) / 64 > kTagLdsCap) return false;
-  if (tile_log2r == 0) return true;
-  const int ncb = grid / (256 >> tile_log2r);
-  return ncb > 0 && ((4 % ncb) == 0 || (ncb % 4) == 0);
-}
-
-// The launch shape of ffmp_raster_ex: cells per block, and the 2-D wave tiles (R rows x (cells per wave
-// task)/R columns) where the plane and the block split into them, else 0: the 1-D chunks.
-void raster_shape(int grid, int32_t cells_per_block, int fmt, int32_t flags, int* cpb_out, int32_t* tile_log2r_out) {
-  const int G2 = grid * grid;
-  const int cpb_max = cells_per_block ? cells_per_block : 4096;
-  const int cpb = G2 < cpb_max ? ((G2 + 1023) / 1024) * 1024 : cpb_max;
-  int32_t tile_log2r = tile_rows_log2(flags);
-  if (tile_log2r) {
-    const int C = (fmt == FMT_CT16 ? 1024 : fmt == FMT_CT8 ? 512 : 256) >> tile_log2r, R = 1 << tile_log2r;
-    const bool whole_bands = cpb >= G2 || (cpb % (grid * R)) == 0;
-    if ((grid % C) != 0 || !whole_bands) tile_log2r = 0;  // the 1-D chunks (identical results)
-  }
-  *cpb_out = cpb;
-  *tile_log2r_out = tile_log2r;
-}
-
-// The granule tags behind an ffmp_obs_t with FFMP_OBS_EXT_TAGS (include/ffmp.h ffmp_obs_tags_t), checked;
-// *on = false without the flag.
-int obs_tags(const ffmp_cfg_t* cfg, const ffmp_obs_t* o, TagArgs* t, bool* on) {
-  *on = (o->reserved & FFMP_OBS_EXT_TAGS) != 0;
-  if (!*on) return FFMP_OK;
-  const ffmp_obs_tags_t* x = reinterpret_cast<const ffmp_obs_tags_t*>(o);
-  if (o->format != FFMP_OBS_F32)
-    return fail(FFMP_E_ARG, "FFMP_OBS_EXT_TAGS: granule tags need format FFMP_OBS_F32, got %d", o->format);
-  if (!x->tags_older || !x->tags_newest) return fail(FFMP_E_ARG, "FFMP_OBS_EXT_TAGS: tags_older / tags_newest is NULL");
-  const int64_t T = ((int64_t)cfg->grid * cfg->grid + FFMP_TAG_CELLS - 1) / FFMP_TAG_CELLS;
-  if (x->tags_env_stride < T)
-    return fail(FFMP_E_ARG, "FFMP_OBS_EXT_TAGS: tags_env_stride %lld < %lld tags per frame",
-                (long long)x->tags_env_stride, (long long)T);
-  *t = TagArgs{x->tags_older, x->tags_newest, x->tags_env_stride};
+// The NULL walls of the entry points that step: the state arrays, the small observations (with the frames'
+// state_m where the launch rasters too) and the step's outputs.
+int check_state(const ffmp_cfg_t* cfg, const ffmp_state_t* st) {
+  if (!st->pose || !st->goal || !st->d0 || !st->t || !st->episode || !st->record || !st->err)
+    return fail(FFMP_E_ARG, "a state pointer is NULL");
+  if (cfg->n_obst > 0 && (!st->obst || !st->obst_r)) return fail(FFMP_E_ARG, "obstacle state NULL");
   return FFMP_OK;
+}
+
+int check_small_obs(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, bool with_state_m) {
+  if ((with_state_m && !obs->state_m) || !obs->state_g || !obs->state_v || !obs->state_t || !obs->grad)
+    return fail(FFMP_E_ARG, "an obs pointer is NULL");
+  if (cfg->n_beams > 0 && !obs->lidar) return fail(FFMP_E_ARG, "obs.lidar NULL with n_beams > 0");
+  return FFMP_OK;
+}
+
+int check_out(const ffmp_out_t* out) {
+  if (!out || !out->reward || !out->done || !out->is_goal || !out->collide || !out->truncated)
+    return fail(FFMP_E_ARG, "an out pointer is NULL");
+  return FFMP_OK;
+}
+
+// Calls launch(tg...) with the tag argument of the plan's kernel: none (no tags), the tags, or the tags as
+// TagArgsW (FFMP_RASTER_WAVES).  The tagged kernels exist for float32 frames, the W ones without flow planes.
+template <int FMT, bool FLOW, class L>
+void launch_tagged_form(const RasterPlan& p, const TagArgs& tg, L&& launch) {
+  if constexpr (FMT == FMT_F32) {
+    if (p.tagged) {
+      if constexpr (!FLOW) {
+        if (p.waves == kRasterWaves) return launch(TagArgsW<kRasterWaves>{tg});
+      }
+      return launch(tg);
+    }
+  }
+  launch();
 }
 
 // The scripted reactive controller of ffmp_policy_reactive: one thread per env reads the env's
@@ -2352,6 +2298,50 @@ void dispatch_variant(int fmt, bool nt, bool xcd, bool fl, F&& f) {
     if (xcd) with_fmt(N{}, T{});
     else with_fmt(N{}, N{});
   }
+}
+
+// The skewed step's instances: one disc per lane on the fewest of 8..64 lanes that hold the discs
+int skew_lanes(const ffmp_cfg_t* cfg) {
+  return cfg->n_obst <= 8 ? 8 : cfg->n_obst <= 16 ? 16 : cfg->n_obst <= 32 ? 32 : 64;
+}
+
+// Calls f(NT, XCD, LPE) with std::integral_constant arguments for the plan's skew_kernel
+template <class F>
+auto skew_variant(const RasterPlan& p, int lpe, F&& f) {
+  using T = std::true_type;
+  using N = std::false_type;
+  auto with_l = [&](auto NT_, auto XCD_) {
+    switch (lpe) {
+      case 8: return f(NT_, XCD_, std::integral_constant<int, 8>{});
+      case 16: return f(NT_, XCD_, std::integral_constant<int, 16>{});
+      case 32: return f(NT_, XCD_, std::integral_constant<int, 32>{});
+      default: return f(NT_, XCD_, std::integral_constant<int, 64>{});
+    }
+  };
+  return p.nt ? (p.xcd ? with_l(T{}, T{}) : with_l(T{}, N{})) : (p.xcd ? with_l(N{}, T{}) : with_l(N{}, N{}));
+}
+
+// The dynamic LDS of a skew_kernel block: the beam minima of its env waves
+size_t skew_keys_bytes(const ffmp_cfg_t* cfg) {
+  return (size_t)4 * (64 / skew_lanes(cfg)) * (size_t)cfg->n_beams * sizeof(uint32_t);
+}
+
+// What ffmp_step_skewed refuses after the plan, still without a pointer of the batch: a block's LDS (the
+// kernel's statics, the staged tags, the beam minima) above the device's limit
+int skew_lds_fit(const ffmp_cfg_t* cfg, const RasterPlan& p) {
+  const size_t static_lds = skew_variant(p, skew_lanes(cfg), [](auto NT_, auto XCD_, auto L_) {
+    static const size_t bytes = [] {
+      hipFuncAttributes a{};
+      return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(
+                                          &skew_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(L_)::value>)) == hipSuccess
+                 ? (size_t)a.sharedSizeBytes
+                 : (size_t)0;
+    }();
+    return bytes;
+  });
+  if (static_lds + (p.tagged ? sizeof(TagLds) : 0) + skew_keys_bytes(cfg) > device_lds_limit())
+    return fail(FFMP_E_ARG, "ffmp_step_skewed: the env waves' LDS does not fit (L = %d)", cfg->n_beams);
+  return FFMP_OK;
 }
 
 }  // namespace
@@ -2476,17 +2466,11 @@ static int launch_env(int mode, bool cmd, const ffmp_cfg_t* cfg, int64_t n, int6
   if (rc) return rc;
   if (n < 0 || env_offset < 0) return fail(FFMP_E_ARG, "negative n or env_offset");
   if (!state || !obs) return fail(FFMP_E_ARG, "state/obs is NULL");
-  if (!state->pose || !state->goal || !state->d0 || !state->t || !state->episode || !state->record || !state->err)
-    return fail(FFMP_E_ARG, "a state pointer is NULL");
-  if (cfg->n_obst > 0 && (!state->obst || !state->obst_r)) return fail(FFMP_E_ARG, "obstacle state NULL");
-  if (!obs->state_g || !obs->state_v || !obs->state_t || !obs->grad)
-    return fail(FFMP_E_ARG, "an obs pointer is NULL");
-  if (cfg->n_beams > 0 && !obs->lidar) return fail(FFMP_E_ARG, "obs.lidar NULL with n_beams > 0");
+  if ((rc = check_state(cfg, state)) || (rc = check_small_obs(cfg, obs, false))) return rc;
   if (mode == kEnvMode_Step) {
     if (!action) return fail(FFMP_E_ARG, cmd ? "cmd is NULL" : "action is NULL");
     if (cmd && ((uintptr_t)action & 15u) != 0) return fail(FFMP_E_ARG, "cmd must be 16-byte aligned");
-    if (!out || !out->reward || !out->done || !out->is_goal || !out->collide || !out->truncated)
-      return fail(FFMP_E_ARG, "an out pointer is NULL");
+    if ((rc = check_out(out))) return rc;
   }
   if (n == 0) return FFMP_OK;
   if (n > 0x7fffffffLL / 64) return fail(FFMP_E_ARG, "n too large for one launch: %lld", (long long)n);  // <= 64 lanes per env
@@ -2521,7 +2505,7 @@ static int launch_env(int mode, bool cmd, const ffmp_cfg_t* cfg, int64_t n, int6
   if (!ok)
     return fail(FFMP_E_ARG, "no env_kernel layout fits the %zu B of LDS a block may use (K = %d, L = %d)",
                 device_lds_limit(), cfg->n_obst, cfg->n_beams);
-  return check_launch(mode == kEnvMode_Scenario ? "ffmp_set_scenario"
+  return launch_ok(mode == kEnvMode_Scenario ? "ffmp_set_scenario"
                       : mode != kEnvMode_Step   ? "ffmp_reset"
                       : cmd                     ? "ffmp_step_state_cmd"
                                                 : "ffmp_step_state");
@@ -2558,39 +2542,17 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
   if (rc) return rc;
   if (n < 0) return fail(FFMP_E_ARG, "negative n");
   if (!record || !obs || !obs->state_m) return fail(FFMP_E_ARG, "record/obs/state_m is NULL");
-  if (cells_per_block != 0 && (cells_per_block < 1024 || cells_per_block % 1024 != 0))
-    return fail(FFMP_E_ARG, "cells_per_block must be 0 or a multiple of 1024, got %d", cells_per_block);
-  if ((flags & FFMP_RASTER_NT) && (flags & FFMP_RASTER_PLAIN)) return fail(FFMP_E_ARG, "NT and PLAIN both set");
-  if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
-  TagArgs tags{};
-  bool tagged = false;
-  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
+  RasterPlan p{};
+  if ((rc = raster_plan(RasterUse::kTwoLaunch, cfg, obs, cells_per_block, flags, n, &p, fail))) return rc;
   if (n == 0) return FFMP_OK;
+  if (p.flow && !obs->flow) return fail(FFMP_E_ARG, "cfg.flow is set but obs.flow is NULL");
   const int G2 = cfg->grid * cfg->grid;
-  const bool ct = obs->format == FFMP_OBS_U8F16;
-  const int fmt = raster_format(ct, cfg->grid, flags);
-  int cpb = 0;
-  int32_t tile_log2r = 0;
-  raster_shape(cfg->grid, cells_per_block, fmt, flags, &cpb, &tile_log2r);
-  const int bpe = (G2 + cpb - 1) / cpb;
+  const int bpe = p.bpe, cpb = p.cpb;
   // a launch holds at most 2^31 - 1 work-items: larger batches go out as several launches over
-  // consecutive env ranges (the whole C5 workload in the compact format is 131,072 x 64 blocks)
+  // consecutive env ranges (the whole C5 workload in the compact format is 131,072 x 64 blocks;
+  // bpe <= 16,384, so a launch always holds an env)
   const int64_t max_envs = (0x7fffffffLL / 256) / bpe;
-  if (max_envs < 1) return fail(FFMP_E_ARG, "a raster plane needs too many blocks: %d", bpe);
-  const bool nt = (flags & FFMP_RASTER_NT) ? true : (flags & FFMP_RASTER_PLAIN) ? false : (G2 <= 16384);
-  const bool xcd = (flags & FFMP_RASTER_XCD) != 0;
-  const bool fl = cfg->flow != 0;
-  if (fl && !obs->flow) return fail(FFMP_E_ARG, "cfg.flow is set but obs.flow is NULL");
-  const int64_t sm_stride = obs->state_m_stride ? obs->state_m_stride : 2 * (int64_t)G2;
-  const int64_t sm_frame = obs->state_m_frame_stride ? obs->state_m_frame_stride : (int64_t)G2;
-  const int64_t sm_frame_abs = sm_frame < 0 ? -sm_frame : sm_frame;  // negative: newest in a lower slot
-  if (sm_stride < (int64_t)G2 || sm_frame_abs < (int64_t)G2 ||
-      (sm_stride < 2 * (int64_t)G2 && sm_frame_abs < n * (int64_t)G2))
-    return fail(FFMP_E_ARG, "state_m strides overlap: env %lld, frame %lld elements (G*G = %d)",
-                (long long)sm_stride, (long long)sm_frame, G2);
-  const int32_t newest = (flags & FFMP_RASTER_NEWEST) ? 1 : 0;
-  const int waves = raster_waves(flags, tagged, ct, fl);
-  const bool direct = raster_direct(flags, tagged, ct, fl, cfg->grid, cpb, tile_log2r);
+  const bool ct = p.ct;
   const dim3 block(256);
   hipStream_t s = (hipStream_t)stream;
   const int64_t rs = rec_stride(cfg->n_obst);
@@ -2599,43 +2561,35 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
     const dim3 grid((unsigned)(m * bpe));
     const float* rec = record + e0 * rs;
     const uint8_t* msk = mask ? mask + e0 : nullptr;
-    float* sm = (float*)((char*)obs->state_m + e0 * sm_stride * (ct ? 1 : 4));
+    float* sm = (float*)((char*)obs->state_m + e0 * p.sm_stride * (ct ? 1 : 4));
     float* pot = obs->potential ? (float*)((char*)obs->potential + e0 * (int64_t)G2 * (ct ? 2 : 4)) : nullptr;
     float* flw = obs->flow ? (float*)((char*)obs->flow + e0 * 2 * (int64_t)G2 * (ct ? 2 : 4)) : nullptr;
-    dispatch_variant(fmt, nt, xcd, fl, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
-      if constexpr (decltype(FMT_)::value == FMT_F32) {
-        if (tagged) {
-          const TagArgs tg{tags.older + e0 * tags.env_stride, tags.newest + e0 * tags.env_stride, tags.env_stride};
-          auto launch = [&](auto t) {
-            hipLaunchKernelGGL((raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, decltype(t)>),
-                               grid, block, tuning().lds_pad, s, *cfg, m, bpe, cpb, rec, msk, sm, sm_stride, sm_frame, newest,
-                               pot, flw, tile_log2r, t);
+    const TagArgs tg{p.tags.older + e0 * p.tags.env_stride, p.tags.newest + e0 * p.tags.env_stride, p.tags.env_stride};
+    dispatch_variant(p.fmt, p.nt, p.xcd, p.flow, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
+      constexpr bool kNT = decltype(NT_)::value, kXCD = decltype(XCD_)::value, kFL = decltype(FL_)::value;
+      constexpr int kFMT = decltype(FMT_)::value;
+      if constexpr (kFMT == FMT_F32 && !kFL) {
+        if (p.direct) {
+          // per launch, once: 1 / G as the kernels compute it, the rows of a block (tiles: whole
+          // bands), and whether lane k's discs may be read as 16-B words
+          const int32_t rpb = (cpb < G2 ? cpb : G2) / cfg->grid;
+          auto go = [&](auto R16_) {
+            hipLaunchKernelGGL((raster_direct_kernel<kNT, kXCD, decltype(R16_)::value>), grid, block, tuning().lds_pad,
+                               s, *cfg, (uint32_t)m, (uint32_t)bpe, cpb, rpb, 1.0f / (float)cfg->grid, rec, msk, sm,
+                               p.sm_stride, p.sm_frame, p.newest, pot, p.tile_log2r, tg);
           };
-          if constexpr (!decltype(FL_)::value) {
-            if (direct) {
-              // per launch, once: 1 / G as the kernels compute it, the rows of a block (tiles: whole
-              // bands), and whether lane k's discs may be read as 16-B words
-              const int32_t rpb = (cpb < G2 ? cpb : G2) / cfg->grid;
-              auto go = [&](auto R16_) {
-                hipLaunchKernelGGL((raster_direct_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(R16_)::value>),
-                                   grid, block, tuning().lds_pad, s, *cfg, (uint32_t)m, (uint32_t)bpe, cpb, rpb,
-                                   1.0f / (float)cfg->grid, rec, msk, sm, sm_stride, sm_frame, newest, pot, tile_log2r, tg);
-              };
-              // every env's record is 64 + 48 K bytes: 16-B aligned with the first
-              if ((reinterpret_cast<uintptr_t>(rec) & 15u) == 0) go(std::true_type{});
-              else go(std::false_type{});
-              return;
-            }
-            if (waves == kRasterWaves) return launch(TagArgsW<kRasterWaves>{tg});
-          }
-          launch(tg);
+          // every env's record is 64 + 48 K bytes: 16-B aligned with the first
+          if ((reinterpret_cast<uintptr_t>(rec) & 15u) == 0) go(std::true_type{});
+          else go(std::false_type{});
           return;
         }
       }
-      hipLaunchKernelGGL((raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value>), grid, block, tuning().lds_pad, s, *cfg, m,
-                         bpe, cpb, rec, msk, sm, sm_stride, sm_frame, newest, pot, flw, tile_log2r);
+      launch_tagged_form<kFMT, kFL>(p, tg, [&](auto... t) {
+        hipLaunchKernelGGL((raster_kernel<kNT, kXCD, kFL, kFMT, decltype(t)...>), grid, block, tuning().lds_pad, s, *cfg, m,
+                           bpe, cpb, rec, msk, sm, p.sm_stride, p.sm_frame, p.newest, pot, flw, p.tile_log2r, t...);
+      });
     });
-    if (int rc2 = check_launch("ffmp_raster")) return rc2;
+    if (int rc2 = launch_ok("ffmp_raster")) return rc2;
   }
   return FFMP_OK;
 }
@@ -2645,9 +2599,8 @@ int ffmp_raster_ex(const ffmp_cfg_t* cfg, int64_t n, const float* record, const 
 static int check_tags_first(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs) {
   if (!cfg || !obs || !(obs->reserved & FFMP_OBS_EXT_TAGS)) return FFMP_OK;
   if (int rc = check_cfg(cfg)) return rc;
-  TagArgs t{};
-  bool on = false;
-  return obs_tags(cfg, obs, &t, &on);
+  RasterPlan p{};
+  return plan_tags(cfg, obs, &p, fail);
 }
 
 int ffmp_raster(const ffmp_cfg_t* cfg, int64_t n, const float* record, const uint8_t* mask, ffmp_obs_t* obs,
@@ -2685,71 +2638,31 @@ static int step_fused(bool cmd, const ffmp_cfg_t* cfg, int64_t n, int64_t env_of
   if (!state || !obs || !action || !out)
     return fail(FFMP_E_ARG, cmd ? "state/obs/cmd/out is NULL" : "state/obs/action/out is NULL");
   if (cmd && ((uintptr_t)action & 15u) != 0) return fail(FFMP_E_ARG, "cmd must be 16-byte aligned");
-  if (!state->pose || !state->goal || !state->d0 || !state->t || !state->episode || !state->record || !state->err)
-    return fail(FFMP_E_ARG, "a state pointer is NULL");
-  if (cfg->n_obst > 0 && (!state->obst || !state->obst_r)) return fail(FFMP_E_ARG, "obstacle state NULL");
-  if (!obs->state_m || !obs->state_g || !obs->state_v || !obs->state_t || !obs->grad)
-    return fail(FFMP_E_ARG, "an obs pointer is NULL");
-  if (cfg->n_beams > 0 && !obs->lidar) return fail(FFMP_E_ARG, "obs.lidar NULL with n_beams > 0");
-  if (!out->reward || !out->done || !out->is_goal || !out->collide || !out->truncated)
-    return fail(FFMP_E_ARG, "an out pointer is NULL");
-  if ((flags & FFMP_RASTER_NT) && (flags & FFMP_RASTER_PLAIN)) return fail(FFMP_E_ARG, "NT and PLAIN both set");
-  const bool fl = cfg->flow != 0;
-  if (fl && !obs->flow) return fail(FFMP_E_ARG, "cfg.flow is set but obs.flow is NULL");
-  if (int rc2 = check_format(obs, fl)) return rc2;
-  TagArgs tags{};
-  bool tagged = false;
-  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
-  const bool ct = obs->format == FFMP_OBS_U8F16;
+  if ((rc = check_state(cfg, state)) || (rc = check_small_obs(cfg, obs, true)) || (rc = check_out(out))) return rc;
+  if (cfg->flow && !obs->flow) return fail(FFMP_E_ARG, "cfg.flow is set but obs.flow is NULL");
+  RasterPlan p{};
+  if ((rc = raster_plan(RasterUse::kOneLaunch, cfg, obs, 0, flags, n, &p, fail))) return rc;
   if (n == 0) return FFMP_OK;
   if (n > 0x7fffffffLL / 256) return fail(FFMP_E_ARG, "n too large for one launch: %lld", (long long)n);  // one block per env
-  const int G2 = cfg->grid * cfg->grid;
-  const int64_t sm_stride = obs->state_m_stride ? obs->state_m_stride : 2 * (int64_t)G2;
-  const int64_t sm_frame = obs->state_m_frame_stride ? obs->state_m_frame_stride : (int64_t)G2;
-  const int64_t sm_frame_abs = sm_frame < 0 ? -sm_frame : sm_frame;  // negative: newest in a lower slot
-  if (sm_stride < (int64_t)G2 || sm_frame_abs < (int64_t)G2 ||
-      (sm_stride < 2 * (int64_t)G2 && sm_frame_abs < n * (int64_t)G2))
-    return fail(FFMP_E_ARG, "state_m strides overlap: env %lld, frame %lld elements (G*G = %d)", (long long)sm_stride,
-                (long long)sm_frame, G2);
-  const bool nt = (flags & FFMP_RASTER_NT) ? true : (flags & FFMP_RASTER_PLAIN) ? false : (G2 <= 16384);
-  const bool xcd = (flags & FFMP_RASTER_XCD) != 0;
-  const int32_t newest = (flags & FFMP_RASTER_NEWEST) ? 1 : 0;
-  const int fmt = raster_format(ct, cfg->grid, flags);
-  const int waves = raster_waves(flags, tagged, ct, fl);
-  int32_t tile_log2r = tile_rows_log2(flags);
-  if (tile_log2r && (cfg->grid % ((fmt == FMT_CT16 ? 1024 : fmt == FMT_CT8 ? 512 : 256) >> tile_log2r)) != 0)
-    tile_log2r = 0;  // a block is one whole plane
   const dim3 grid((unsigned)n), block(256);
   hipStream_t s = (hipStream_t)stream;
   ffmp_out_t o = *out;
-  dispatch_variant(fmt, nt, xcd, fl, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
-    if constexpr (decltype(FMT_)::value == FMT_F32) {
-      if (tagged) {
-        auto launch = [&](auto t) {
-          if (cmd)
-            hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, true, decltype(t)>),
-                               grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const double2*>(action), *state,
-                               *obs, o, sm_stride, sm_frame, newest, tile_log2r, t);
-          else
-            hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, FMT_F32, false, decltype(t)>),
-                               grid, block, tuning().lds_pad, s, *cfg, n, env_offset, static_cast<const int64_t*>(action), *state,
-                               *obs, o, sm_stride, sm_frame, newest, tile_log2r, t);
-        };
-        if constexpr (!decltype(FL_)::value) {
-          if (waves == kRasterWaves) return launch(TagArgsW<kRasterWaves>{tags});
-        }
-        launch(tags);
-        return;
-      }
-    }
-    if (cmd)
-      hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value, true>), grid, block, tuning().lds_pad, s, *cfg, n,
-                         env_offset, static_cast<const double2*>(action), *state, *obs, o, sm_stride, sm_frame, newest, tile_log2r);
-    else
-      hipLaunchKernelGGL((step_raster_kernel<decltype(NT_)::value, decltype(XCD_)::value, decltype(FL_)::value, decltype(FMT_)::value, false>), grid, block, tuning().lds_pad, s, *cfg, n,
-                         env_offset, static_cast<const int64_t*>(action), *state, *obs, o, sm_stride, sm_frame, newest, tile_log2r);
+  const TagArgs tg{p.tags.older, p.tags.newest, p.tags.env_stride};
+  dispatch_variant(p.fmt, p.nt, p.xcd, p.flow, [&](auto NT_, auto XCD_, auto FL_, auto FMT_) {
+    constexpr bool kNT = decltype(NT_)::value, kXCD = decltype(XCD_)::value, kFL = decltype(FL_)::value;
+    constexpr int kFMT = decltype(FMT_)::value;
+    launch_tagged_form<kFMT, kFL>(p, tg, [&](auto... t) {
+      if (cmd)
+        hipLaunchKernelGGL((step_raster_kernel<kNT, kXCD, kFL, kFMT, true, decltype(t)...>), grid, block, tuning().lds_pad,
+                           s, *cfg, n, env_offset, static_cast<const double2*>(action), *state, *obs, o, p.sm_stride,
+                           p.sm_frame, p.newest, p.tile_log2r, t...);
+      else
+        hipLaunchKernelGGL((step_raster_kernel<kNT, kXCD, kFL, kFMT, false, decltype(t)...>), grid, block, tuning().lds_pad,
+                           s, *cfg, n, env_offset, static_cast<const int64_t*>(action), *state, *obs, o, p.sm_stride,
+                           p.sm_frame, p.newest, p.tile_log2r, t...);
+    });
   });
-  return check_launch(cmd ? "ffmp_step_fused_cmd" : "ffmp_step_fused");
+  return launch_ok(cmd ? "ffmp_step_fused_cmd" : "ffmp_step_fused");
 }
 
 int ffmp_step_fused(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action,
@@ -2770,157 +2683,82 @@ int ffmp_step_fused_cmd(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, co
 #endif
 static constexpr double kSkewEnvSpan = FFMP_SKEW_ENV_SPAN;
 
-// ffmp_step_skewed; dry_run: every check (the LDS fit included), no launch (ffmp_step_skewed_check)
-static int step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action_next,
-                       ffmp_state_t* state_next, ffmp_obs_t* obs, ffmp_out_t* out, const float* record_raster,
-                       int32_t cells_per_block, int32_t flags, void* stream, bool dry_run) {
+int ffmp_step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action_next,
+                     ffmp_state_t* state_next, ffmp_obs_t* obs, ffmp_out_t* out, const float* record_raster,
+                     int32_t cells_per_block, int32_t flags, void* stream) {
   int rc = check_cfg(cfg);
   if (rc) return rc;
   if (n < 0 || env_offset < 0) return fail(FFMP_E_ARG, "negative n or env_offset");
   if (!state_next || !obs || !action_next || !out || !record_raster)
     return fail(FFMP_E_ARG, "state/obs/action/out/record_raster is NULL");
-  if (!state_next->pose || !state_next->goal || !state_next->d0 || !state_next->t || !state_next->episode ||
-      !state_next->record || !state_next->err)
-    return fail(FFMP_E_ARG, "a state pointer is NULL");
+  if ((rc = check_state(cfg, state_next))) return rc;
   if (state_next->record == record_raster)
     return fail(FFMP_E_ARG, "ffmp_step_skewed: the env step must write the other record buffer");
-  if (cfg->n_obst > 0 && (!state_next->obst || !state_next->obst_r)) return fail(FFMP_E_ARG, "obstacle state NULL");
-  if (!obs->state_m || !obs->state_g || !obs->state_v || !obs->state_t || !obs->grad)
-    return fail(FFMP_E_ARG, "an obs pointer is NULL");
-  if (cfg->n_beams > 0 && !obs->lidar) return fail(FFMP_E_ARG, "obs.lidar NULL with n_beams > 0");
-  if (!out->reward || !out->done || !out->is_goal || !out->collide || !out->truncated)
-    return fail(FFMP_E_ARG, "an out pointer is NULL");
-  if ((flags & FFMP_RASTER_NT) && (flags & FFMP_RASTER_PLAIN)) return fail(FFMP_E_ARG, "NT and PLAIN both set");
-  if (cells_per_block != 0 && (cells_per_block < 1024 || cells_per_block % 1024 != 0))
-    return fail(FFMP_E_ARG, "cells_per_block must be 0 or a multiple of 1024, got %d", cells_per_block);
-  if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
-  // the instances there are: float32 frames, no flow planes, one disc per lane on 8..64 lanes
-  if (obs->format != FFMP_OBS_F32 || cfg->flow) return fail(FFMP_E_ARG, "ffmp_step_skewed: float32 frames without flow planes only");
-  TagArgs tags{};
-  bool tagged = false;
-  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
-  const int lpe = cfg->n_obst <= 8 ? 8 : cfg->n_obst <= 16 ? 16 : cfg->n_obst <= 32 ? 32 : 64;
+  if ((rc = check_small_obs(cfg, obs, true)) || (rc = check_out(out))) return rc;
+  RasterPlan p{};
+  if ((rc = raster_plan(RasterUse::kSkewed, cfg, obs, cells_per_block, flags, n, &p, fail))) return rc;
   if (n == 0) return FFMP_OK;
-  const int G2 = cfg->grid * cfg->grid;
-  const int cpb_max = cells_per_block ? cells_per_block : 4096;
-  const int cpb = G2 < cpb_max ? ((G2 + 1023) / 1024) * 1024 : cpb_max;
-  const int bpe = (G2 + cpb - 1) / cpb;
+  const int lpe = skew_lanes(cfg);
   const int64_t env_per_block = 4 * (64 / lpe);
   const int64_t env_chunks = ((n + env_per_block - 1) / env_per_block + 7) / 8;  // 8 env blocks each
-  const int64_t ras_blocks = n * bpe;
+  const int64_t ras_blocks = n * p.bpe;
   // the env blocks spread over the first kSkewEnvSpan of the raster's blocks
   const int64_t chunk_s = std::max<int64_t>(0, (int64_t)(kSkewEnvSpan * (double)ras_blocks) / (8 * env_chunks));
   if (ras_blocks + 8 * env_chunks > 0x7fffffffLL / 256) return fail(FFMP_E_ARG, "ffmp_step_skewed: n too large for one launch");
   if (env_chunks * 8 * chunk_s > ras_blocks) return fail(FFMP_E_ARG, "ffmp_step_skewed: block layout");
-  const int64_t sm_stride = obs->state_m_stride ? obs->state_m_stride : 2 * (int64_t)G2;
-  const int64_t sm_frame = obs->state_m_frame_stride ? obs->state_m_frame_stride : (int64_t)G2;
-  const int64_t sm_frame_abs = sm_frame < 0 ? -sm_frame : sm_frame;
-  if (sm_stride < (int64_t)G2 || sm_frame_abs < (int64_t)G2 ||
-      (sm_stride < 2 * (int64_t)G2 && sm_frame_abs < n * (int64_t)G2))
-    return fail(FFMP_E_ARG, "state_m strides overlap: env %lld, frame %lld elements (G*G = %d)", (long long)sm_stride,
-                (long long)sm_frame, G2);
-  const bool nt = (flags & FFMP_RASTER_NT) ? true : (flags & FFMP_RASTER_PLAIN) ? false : (G2 <= 16384);
-  const bool xcd = (flags & FFMP_RASTER_XCD) != 0;
-  const int32_t newest = (flags & FFMP_RASTER_NEWEST) ? 1 : 0;
-  int32_t tile_log2r = tile_rows_log2(flags);
-  if (tile_log2r) {
-    const int C = 256 >> tile_log2r, R = 1 << tile_log2r;
-    const bool whole_bands = cpb >= G2 || (cpb % (cfg->grid * R)) == 0;
-    if ((cfg->grid % C) != 0 || !whole_bands) tile_log2r = 0;
-  }
-  const size_t keys = (size_t)4 * (64 / lpe) * (size_t)cfg->n_beams * sizeof(uint32_t);
+  if ((rc = skew_lds_fit(cfg, p))) return rc;
+  const size_t keys = skew_keys_bytes(cfg);
   const dim3 grid((unsigned)(ras_blocks + 8 * env_chunks)), block(256);
   hipStream_t s = (hipStream_t)stream;
   ffmp_out_t o = *out;
-  auto go = [&](auto NT_, auto XCD_, auto L_) {
+  const TagArgs tg{p.tags.older, p.tags.newest, p.tags.env_stride};
+  skew_variant(p, lpe, [&](auto NT_, auto XCD_, auto L_) {
     constexpr bool kNT = decltype(NT_)::value, kXCD = decltype(XCD_)::value;
     constexpr int kL = decltype(L_)::value;
-    static const size_t static_lds = [] {
-      hipFuncAttributes a{};
-      return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&skew_kernel<kNT, kXCD, kL>)) == hipSuccess
-                 ? (size_t)a.sharedSizeBytes
-                 : (size_t)0;
-    }();
-    if (static_lds + (tagged ? sizeof(TagLds) : 0) + keys > device_lds_limit()) return false;
-    if (dry_run) return true;
-    if (tagged) {
+    if (p.tagged)
       hipLaunchKernelGGL((skew_kernel<kNT, kXCD, kL, TagArgs>), grid, block, keys, s, *cfg, n, env_offset, action_next,
-                         *state_next, *obs, o, (int32_t)env_chunks, (int32_t)chunk_s, bpe, cpb, record_raster, sm_stride,
-                         sm_frame, newest, tile_log2r, tags);
-      return true;
-    }
-    hipLaunchKernelGGL((skew_kernel<kNT, kXCD, kL>), grid, block, keys, s, *cfg, n, env_offset, action_next, *state_next,
-                       *obs, o, (int32_t)env_chunks, (int32_t)chunk_s, bpe, cpb, record_raster, sm_stride, sm_frame,
-                       newest, tile_log2r);
-    return true;
-  };
-  using T = std::true_type;
-  using N = std::false_type;
-  auto with_l = [&](auto NT_, auto XCD_) {
-    switch (lpe) {
-      case 8: return go(NT_, XCD_, std::integral_constant<int, 8>{});
-      case 16: return go(NT_, XCD_, std::integral_constant<int, 16>{});
-      case 32: return go(NT_, XCD_, std::integral_constant<int, 32>{});
-      default: return go(NT_, XCD_, std::integral_constant<int, 64>{});
-    }
-  };
-  const bool ok = nt ? (xcd ? with_l(T{}, T{}) : with_l(T{}, N{})) : (xcd ? with_l(N{}, T{}) : with_l(N{}, N{}));
-  if (!ok) return fail(FFMP_E_ARG, "ffmp_step_skewed: the env waves' LDS does not fit (L = %d)", cfg->n_beams);
-  if (dry_run) return FFMP_OK;
-  return check_launch("ffmp_step_skewed");
+                         *state_next, *obs, o, (int32_t)env_chunks, (int32_t)chunk_s, p.bpe, p.cpb, record_raster,
+                         p.sm_stride, p.sm_frame, p.newest, p.tile_log2r, tg);
+    else
+      hipLaunchKernelGGL((skew_kernel<kNT, kXCD, kL>), grid, block, keys, s, *cfg, n, env_offset, action_next, *state_next,
+                         *obs, o, (int32_t)env_chunks, (int32_t)chunk_s, p.bpe, p.cpb, record_raster, p.sm_stride,
+                         p.sm_frame, p.newest, p.tile_log2r);
+    return 0;
+  });
+  return launch_ok("ffmp_step_skewed");
 }
 
-int ffmp_step_skewed(const ffmp_cfg_t* cfg, int64_t n, int64_t env_offset, const int64_t* action_next,
-                     ffmp_state_t* state_next, ffmp_obs_t* obs, ffmp_out_t* out, const float* record_raster,
-                     int32_t cells_per_block, int32_t flags, void* stream) {
-  return step_skewed(cfg, n, env_offset, action_next, state_next, obs, out, record_raster, cells_per_block, flags,
-                     stream, false);
+// The queries: the plan of a launch with these arguments (no batch: nothing but the obs header is read).
+// NT with PLAIN bears on neither answer and is not refused here.
+static int query_plan(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t cells_per_block, int32_t flags, RasterPlan* p) {
+  int rc = check_cfg(cfg);
+  if (rc) return rc;
+  if (!obs) return fail(FFMP_E_ARG, "obs is NULL");
+  return raster_plan(RasterUse::kTwoLaunch, cfg, obs, cells_per_block, flags & ~(FFMP_RASTER_NT | FFMP_RASTER_PLAIN), 0, p, fail);
 }
 
 int ffmp_raster_waves(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t flags) {
-  int rc = check_cfg(cfg);
-  if (rc) return rc;
-  if (!obs) return fail(FFMP_E_ARG, "obs is NULL");
-  if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
-  TagArgs tags{};
-  bool tagged = false;
-  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
-  return raster_waves(flags, tagged, obs->format == FFMP_OBS_U8F16, cfg->flow != 0);
+  RasterPlan p{};
+  if (int rc = query_plan(cfg, obs, 0, flags, &p)) return rc;
+  return p.waves;
 }
 
 int ffmp_raster_direct(const ffmp_cfg_t* cfg, const ffmp_obs_t* obs, int32_t cells_per_block, int32_t flags) {
-  int rc = check_cfg(cfg);
-  if (rc) return rc;
-  if (!obs) return fail(FFMP_E_ARG, "obs is NULL");
-  if (int rc2 = check_format(obs, cfg->flow != 0)) return rc2;
-  TagArgs tags{};
-  bool tagged = false;
-  if (int rc2 = obs_tags(cfg, obs, &tags, &tagged)) return rc2;
-  const bool ct = obs->format == FFMP_OBS_U8F16;
-  if (cells_per_block != 0 && (cells_per_block < 1024 || cells_per_block % 1024 != 0))
-    return fail(FFMP_E_ARG, "cells_per_block must be 0 or a multiple of 1024, got %d", cells_per_block);
-  int cpb = 0;
-  int32_t tile_log2r = 0;
-  raster_shape(cfg->grid, cells_per_block, raster_format(ct, cfg->grid, flags), flags, &cpb, &tile_log2r);
-  return raster_direct(flags, tagged, ct, cfg->flow != 0, cfg->grid, cpb, tile_log2r) ? 1 : 0;
+  RasterPlan p{};
+  if (int rc = query_plan(cfg, obs, cells_per_block, flags, &p)) return rc;
+  return p.direct ? 1 : 0;
 }
 
 int ffmp_step_skewed_check(const ffmp_cfg_t* cfg, int32_t format, int32_t flags) {
   int rc = check_cfg(cfg);
   if (rc) return rc;
+  // (an unknown format too: there is no obs to call it unknown in)
   if (format != FFMP_OBS_F32 || cfg->flow) return fail(FFMP_E_ARG, "ffmp_step_skewed: float32 frames without flow planes only");
-  if (cfg->n_obst > FFMP_MAX_OBST) return fail(FFMP_E_ARG, "n_obst > FFMP_MAX_OBST");
-  // the launch's own checks on a placeholder batch of one env, stopped before the launch
-  static double dummy[8];
-  static float fdummy[64];
-  static int32_t idummy[2];
-  static uint32_t udummy[1];
-  static uint8_t bdummy[4];
-  static int64_t adummy[1];
-  ffmp_state_t st{dummy, dummy, dummy, dummy, dummy, idummy, idummy, fdummy, udummy, nullptr, nullptr};
-  ffmp_obs_t ob{fdummy, fdummy, fdummy, fdummy, nullptr, fdummy, fdummy, nullptr, 0, 0, FFMP_OBS_F32, 0};
-  ffmp_out_t o{fdummy, bdummy, bdummy + 1, bdummy + 2, bdummy + 3};
-  return step_skewed(cfg, 1, 0, adummy, &st, &ob, &o, fdummy + 32, 0, flags & ~FFMP_RASTER_NEWEST, nullptr, true);
+  ffmp_obs_t ob{};  // a launch's obs header: default strides, no tags
+  ob.format = format;
+  RasterPlan p{};
+  if ((rc = raster_plan(RasterUse::kSkewed, cfg, &ob, 0, flags, 1, &p, fail))) return rc;
+  return skew_lds_fit(cfg, p);
 }
 
 int ffmp_reward_done(const ffmp_cfg_t* cfg, int64_t n, const double* scan, int32_t scan_len,
@@ -2938,7 +2776,7 @@ int ffmp_reward_done(const ffmp_cfg_t* cfg, int64_t n, const double* scan, int32
   hipLaunchKernelGGL(reward_done_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *cfg, n, scan,
                      scan_len, local_map, map_stride, collide_in, goal_in, rel_goal, is_first, d0, reward,
                      done, is_goal, collide);
-  return check_launch("ffmp_reward_done");
+  return launch_ok("ffmp_reward_done");
 }
 
 int ffmp_reward_done_packed(const ffmp_cfg_t* cfg, void* host_buf, void* dev_buf, int64_t in_bytes, int32_t scan_len,
@@ -2971,7 +2809,7 @@ int ffmp_reward_done_packed(const ffmp_cfg_t* cfg, void* host_buf, void* dev_buf
       a.goal_in = (uint8_t)h[42];
       a.flags = (uint8_t)(flags & 3);
       hipLaunchKernelGGL(reward_done_args_kernel, dim3(1), dim3(64), 0, s, a, (uint8_t*)out_dev);
-      if (int rc = check_launch("ffmp_reward_done_packed")) return rc;
+      if (int rc = launch_ok("ffmp_reward_done_packed")) return rc;
       const hipError_t e = hipStreamSynchronize(s);
       if (e != hipSuccess) return fail(FFMP_E_HIP, "ffmp_reward_done_packed: %s", hipGetErrorString(e));
       return FFMP_OK;
@@ -3003,7 +2841,7 @@ int ffmp_footprint_collision(const ffmp_cfg_t* cfg, int64_t n, const float* loca
   if (n == 0) return FFMP_OK;
   hipLaunchKernelGGL(footprint_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      *cfg, n, local_map, map_stride, collide);
-  return check_launch("ffmp_footprint_collision");
+  return launch_ok("ffmp_footprint_collision");
 }
 
 int ffmp_scan_collision(int64_t n, int32_t L, const float* ranges, double thr, uint8_t* collide, float* min_r,
@@ -3025,7 +2863,7 @@ int ffmp_check_exact_math(int32_t which, uint32_t lo_bits, uint32_t hi_bits, uns
   const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255) / 256, 65536);
   hipLaunchKernelGGL(exact_math_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, which, lo_bits, hi_bits,
                      mismatches, first_bits);
-  return check_launch("ffmp_check_exact_math");
+  return launch_ok("ffmp_check_exact_math");
 }
 
 int ffmp_episode_init(int64_t n, const uint8_t* mask, int32_t flags, ffmp_episode_t* ep, void* stream) {
@@ -3037,7 +2875,7 @@ int ffmp_episode_init(int64_t n, const uint8_t* mask, int32_t flags, ffmp_episod
   if (n == 0) return FFMP_OK;
   hipLaunchKernelGGL(episode_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
                      mask, flags, *ep);
-  return check_launch("ffmp_episode_init");
+  return launch_ok("ffmp_episode_init");
 }
 
 int ffmp_episode_update(int64_t n, const ffmp_out_t* out, int32_t window, int32_t max_steps, double threshold,
@@ -3051,7 +2889,7 @@ int ffmp_episode_update(int64_t n, const ffmp_out_t* out, int32_t window, int32_
   if (n == 0) return FFMP_OK;
   hipLaunchKernelGGL(episode_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      n, *out, window, max_steps, threshold, flags, *ep);
-  return check_launch("ffmp_episode_update");
+  return launch_ok("ffmp_episode_update");
 }
 
 int ffmp_temporal_maps(int64_t n, const void* frames, const int64_t* lag_offset, int32_t k, int64_t env_stride,
@@ -3076,7 +2914,7 @@ int ffmp_temporal_maps(int64_t n, const void* frames, const int64_t* lag_offset,
   if (n * k * chunks > 0x7fffffffLL) return fail(FFMP_E_ARG, "too many blocks for one launch");
   hipLaunchKernelGGL(temporal_maps_kernel, dim3((unsigned)(n * k * chunks)), dim3(256), 0, (hipStream_t)stream,
                      (const char*)frames, lag, k, env_b, plane_b, since, (int32_t)chunks, (char*)out);
-  return check_launch("ffmp_temporal_maps");
+  return launch_ok("ffmp_temporal_maps");
 }
 
 int ffmp_bev_image(int64_t n, int32_t compact, const void* occ, int64_t occ_env_stride, const void* flow,
@@ -3106,7 +2944,7 @@ int ffmp_bev_image(int64_t n, int32_t compact, const void* occ, int64_t occ_env_
   else
     hipLaunchKernelGGL((bev_image_kernel<false, 1>), grid, dim3(256), 0, s, n, occ, occ_env_stride, flow, plane,
                        (int32_t)chunks, vmax, out, out_env_stride);
-  return check_launch("ffmp_bev_image");
+  return launch_ok("ffmp_bev_image");
 }
 
 int ffmp_policy_reactive(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, int64_t* action, void* stream) {
@@ -3131,7 +2969,7 @@ int ffmp_policy_reactive(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs
     hipLaunchKernelGGL(policy_reactive_kernel<uint8_t>, grid, block, 0, s, n, cfg->grid,
                        reinterpret_cast<const uint8_t*>(obs->state_m) + frame, env_stride, obs->state_g, look0, look1,
                        1.0f, action);
-  return check_launch("ffmp_policy_reactive");
+  return launch_ok("ffmp_policy_reactive");
 }
 
 int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, double* cmd, void* stream) {
@@ -3146,7 +2984,7 @@ int ffmp_policy_field(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs, d
   if (n > 0x7fffffffLL) return fail(FFMP_E_ARG, "n too large for one launch: %lld", (long long)n);
   hipLaunchKernelGGL(policy_field_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n,
                      cfg->dt, obs->grad, reinterpret_cast<double2*>(cmd));
-  return check_launch("ffmp_policy_field");
+  return launch_ok("ffmp_policy_field");
 }
 
 #ifdef FFMP_TRACE

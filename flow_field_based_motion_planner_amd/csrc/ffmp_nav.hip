@@ -43,14 +43,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "ffmp.h"
+#include "ffmp_host.h"
 
 #pragma clang fp contract(off)
-
-namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
-}
-using ffmp_detail::fail;
 
 namespace {
 
@@ -807,9 +802,7 @@ int nav_launch(const NavArgs& a, const NavFoot& foot, int64_t n, const T* newest
     }
   }
   hipLaunchKernelGGL(k, dim3((unsigned)n), dim3(kNavThreads), lds, s, a, foot, newest, goal);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "ffmp_nav_field: HIP launch failed: %s", hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok("ffmp_nav_field");
 }
 
 const void* nav_tiled_fn(bool u8, bool vec) {
@@ -970,9 +963,7 @@ int ffmp_nav_field_tiled(const ffmp_cfg_t* cfg, int64_t n, const ffmp_obs_t* obs
     if (vec) hipLaunchKernelGGL((nav_field_tiled_kernel<uint8_t, true>), dim3((unsigned)slots), dim3(kNavThreads), lds, s, a, ta, foot, newest, goal_ego);
     else hipLaunchKernelGGL((nav_field_tiled_kernel<uint8_t, false>), dim3((unsigned)slots), dim3(kNavThreads), lds, s, a, ta, foot, newest, goal_ego);
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok(who);
 }
 
 int ffmp_nav_field_check(const ffmp_cfg_t* cfg, int32_t format, int32_t margin, int32_t soft_pen, int32_t lookahead) {

@@ -32,13 +32,9 @@
 #include <type_traits>
 
 #include "ffmp_device.h"
+#include "ffmp_host.h"
 
 #pragma clang fp contract(off)
-
-namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
-}
-using ffmp_detail::fail;
 
 namespace {
 
@@ -349,9 +345,7 @@ int ffmp_flow_predict(const ffmp_cfg_t* cfg, int64_t n, const void* frame, int64
     }
   }
   hipLaunchKernelGGL(k, dim3((unsigned)n), dim3(kPredThreads), lds, (hipStream_t)stream, a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok(who);
 }
 
 }  // extern "C"

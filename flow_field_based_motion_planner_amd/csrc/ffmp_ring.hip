@@ -11,11 +11,9 @@
 #include <mutex>
 #include <vector>
 
-#include "ffmp.h"
+#include "ffmp_host.h"
 
 namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
-
 // FFMP_TUNE_RING_EXTRA: fresh pieces beyond need per create / rebuild (0 = default, v = cap v - 1)
 std::atomic<int32_t> g_ring_extra{0};
 // bytes of virtual address space reserved so far per device (never freed: see ffmp_ring_va_reserved)
@@ -26,7 +24,6 @@ void note_va(int32_t device, size_t bytes) {
 }
 int32_t ring_extra_swap(int32_t v) { return g_ring_extra.exchange(v); }
 }
-using ffmp_detail::fail;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

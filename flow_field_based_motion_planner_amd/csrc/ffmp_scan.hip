@@ -40,13 +40,9 @@
 #include <stdint.h>
 
 #include "ffmp_device.h"
+#include "ffmp_host.h"
 
 #pragma clang fp contract(off)
-
-namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
-}
-using ffmp_detail::fail;
 
 namespace {
 
@@ -449,9 +445,7 @@ int ffmp_scan_frames(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int6
     hipLaunchKernelGGL((scan_kernel<FFMP_OBS_F32>), dim3((unsigned)blocks), dim3(kScanThreads), 0, s, *cfg, a);
   else
     hipLaunchKernelGGL((scan_kernel<FFMP_OBS_U8F16>), dim3((unsigned)blocks), dim3(kScanThreads), 0, s, *cfg, a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok(who);
 }
 
 int ffmp_scan_map_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t format, int32_t unknown, float thickness,
@@ -534,9 +528,7 @@ int ffmp_scan_map(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t
     hipLaunchKernelGGL((scan_map_kernel<FFMP_OBS_F32>), dim3((unsigned)blocks), dim3(kScanThreads), 0, s, *cfg, a);
   else
     hipLaunchKernelGGL((scan_map_kernel<FFMP_OBS_U8F16>), dim3((unsigned)blocks), dim3(kScanThreads), 0, s, *cfg, a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok(who);
 }
 
 }  // extern "C"

@@ -30,13 +30,9 @@
 #include <stdint.h>
 
 #include "ffmp_device.h"
+#include "ffmp_host.h"
 
 #pragma clang fp contract(off)
-
-namespace ffmp_detail {
-int fail(int code, const char* fmt, ...);  // ffmp_kernels.hip (sets ffmp_last_error())
-}
-using ffmp_detail::fail;
 
 namespace {
 
@@ -297,9 +293,7 @@ int ffmp_visible_frames(const ffmp_cfg_t* cfg, int64_t n, const float* record, i
     hipLaunchKernelGGL((visible_kernel<FFMP_OBS_F32>), dim3((unsigned)blocks), dim3(kVisThreads), 0, s, *cfg, a);
   else
     hipLaunchKernelGGL((visible_kernel<FFMP_OBS_U8F16>), dim3((unsigned)blocks), dim3(kVisThreads), 0, s, *cfg, a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(FFMP_E_HIP, "%s: HIP launch failed: %s", who, hipGetErrorString(err));
-  return FFMP_OK;
+  return launch_ok(who);
 }
 
 }  // extern "C"

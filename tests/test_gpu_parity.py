@@ -306,8 +306,11 @@ def test_autotune_picks_a_candidate():
     cfg = FFMPConfig(grid=128, n_obst=8, n_beams=0, seed=3)
     env = FFMPVec(8192, cfg, device="cuda:0")  # 8192 x 3 x 64 KiB planes > AUTOTUNE_MIN_BYTES
     assert env.placement is not None
-    assert tuple(env.raster_shape) in FFMPVec.RASTER_SHAPES
-    assert env.frame_window == 8 and tuple(env.raster_shape_newest) in FFMPVec.RASTER_SHAPES
+    # what the autotune ranks: the offered RASTER_SHAPES and, with the default granule tags, DIRECT_SHAPES
+    cands = env._shape_candidates()
+    assert env.frame_tags is not None and set(cands) <= set(FFMPVec.RASTER_SHAPES + FFMPVec.DIRECT_SHAPES)
+    assert tuple(env.raster_shape) in cands
+    assert env.frame_window == 8 and tuple(env.raster_shape_newest) in cands
     with pytest.raises(RuntimeError):
         env.step(torch.zeros(8192, dtype=torch.int64, device="cuda:0"))  # autotune leaves it un-reset
     env.reset()
