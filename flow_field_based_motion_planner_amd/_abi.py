@@ -166,6 +166,9 @@ _SIGS = {
     "ffmp_flow_predict": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _I64, _I32, _P, _P, _I64, _P, _I32,
                                     C.c_float, _I32, _I32, _I32, _I32, _P]),
     "ffmp_flow_predict_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, _I32, _I32, _I32, _I32]),
+    "ffmp_frame_potential": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _I64, _P, _I32, _I32, _P, _I64, _P, _I64, _I32,
+                                       _P, _P, _P]),
+    "ffmp_frame_potential_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

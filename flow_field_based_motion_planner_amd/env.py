@@ -425,6 +425,14 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before predicted_frames()")
         return self._vec_env().predicted_frames(**kw)
 
+    def frame_potential(self, **kw):
+        """The potential field of an occupancy frame of this one env (FFMPVec.frame_potential,
+        include/ffmp.h ffmp_frame_potential): a dict of device tensors with a leading 1 — grad (1, 2),
+        robot_d2 (1,), clearance (1,), potential (1, G, G), and dist2 (1, G, G) with distance=True."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before frame_potential()")
+        return self._vec_env().frame_potential(**kw)
+
     def render(self, mode="human"):
         return None
 

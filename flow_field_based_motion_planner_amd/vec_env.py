@@ -1675,13 +1675,20 @@ class FFMPVec:
                                                      out.data_ptr(), self._stream()), "ffmp_policy_reactive")
         return out
 
-    def policy_field(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def policy_field(self, out: Optional[torch.Tensor] = None, grad: Optional[torch.Tensor] = None,
+                     frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False,
+                     lidar_map: Optional["LidarMap"] = None, predict=False) -> torch.Tensor:
         """The next (v, w) commands (N, 2) float64 from the current observation, on the device
         (include/ffmp.h ffmp_policy_field): descend the potential field along its gradient at the
         robot cell (obs["grad"]) — full speed along the descent direction's heading component, turn
         towards it, turn on the spot when it points behind.  A scripted controller for closed-loop
         runs over commands, as policy_reactive is over action ids.  `out`: write into this (N, 2)
-        float64 tensor (e.g. command_buffer) instead of a new one."""
+        float64 tensor (e.g. command_buffer) instead of a new one.
+        grad: follow this contiguous (N, 2) float32 device tensor instead of obs["grad"] (e.g.
+        frame_potential(...)["grad"]).  frames / visible / lidar / lidar_map / predict: follow the
+        field of that plane — frame_potential's gradient with its defaults (one more launch, plus
+        the plane's own), the follower a robot with nothing but its scan can run.  With none of
+        them the call is what it always was."""
         self._check_open()
         if self._needs_reset:
             raise RuntimeError("call reset() before policy_field()")
@@ -1693,8 +1700,23 @@ class FFMPVec:
                 or out.device != self.device or out.data_ptr() % 16:
             raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape "
                              f"({self.num_envs}, 2) on {self.device}")
+        obs_c = self._obs_c
+        sensed = frames is not None or visible or lidar or lidar_map is not None or (predict is not False and predict is not None)
+        if grad is not None and sensed:
+            raise ValueError("policy_field: pass grad or a plane (frames, visible, lidar, lidar_map, predict), not both")
+        if sensed:
+            grad = torch.empty((self.num_envs, 2), dtype=torch.float32, device=self.device)
+            plane = self._plane_source("policy_field", frames, visible, lidar, lidar_map, predict)
+            self._potential_launch(plane, None, 255, self._potential_reach("policy_field", None, True), grad=grad)
+        elif grad is not None and (not isinstance(grad, torch.Tensor) or tuple(grad.shape) != (self.num_envs, 2)
+                                   or grad.dtype != torch.float32 or not grad.is_contiguous() or grad.device != self.device):
+            raise ValueError(f"grad must be a contiguous float32 tensor of shape ({self.num_envs}, 2) on {self.device}")
+        if grad is not None:
+            obs_c = _abi.ObsT()
+            C.memmove(C.byref(obs_c), C.byref(self._obs_c), C.sizeof(obs_c))
+            obs_c.grad, obs_c.reserved = grad.data_ptr(), 0  # a plain ffmp_obs_t: only grad is read
         with torch.cuda.device(self.device):
-            _abi.check(self.lib.ffmp_policy_field(C.byref(self._cfg_c), self.num_envs, C.byref(self._obs_c),
+            _abi.check(self.lib.ffmp_policy_field(C.byref(self._cfg_c), self.num_envs, C.byref(obs_c),
                                                   out.data_ptr(), self._stream()), "ffmp_policy_field")
         return out
 
@@ -1751,20 +1773,9 @@ class FFMPVec:
         ob.format, ob.reserved = fmts[frames.dtype], 0
         return ob
 
-    def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
-                    cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None,
-                    frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False,
-                    lidar_map: Optional["LidarMap"] = None, predict=False) -> None:
-        """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
-        observation: the newest frame through the window's strides and format, the ego goal from
-        record words 8..9.  frames: plan over this (N, G, G) plane instead of the newest frame;
-        visible: over visible_frames(newest_only=True, unknown=0); lidar: over
-        lidar_frames(newest_only=True, unknown=0); lidar_map: over that LidarMap's frame; predict:
-        over predicted_frames() (True), predicted_frames(**predict) (a dict) or
-        predicted_frames(flow=predict) (a LidarFlow)."""
-        self._check_open()
-        if self._needs_reset:
-            raise RuntimeError(f"call reset() before {what}()")
+    def _plane_source(self, what: str, frames, visible: bool, lidar: bool, lidar_map, predict) -> Optional[torch.Tensor]:
+        """The plane a caller of nav_field's conventions asks for — frames=, visible=True, lidar=True,
+        lidar_map= or predict=, at most one — or None for the newest frame of the window."""
         if predict is not False and predict is not None:
             if frames is not None or visible or lidar or lidar_map is not None:
                 raise ValueError(f"{what}: pass one of frames, visible=True, lidar=True, lidar_map and predict")
@@ -1794,6 +1805,23 @@ class FFMPVec:
             if not isinstance(lidar_map, LidarMap) or lidar_map.env is not self or lidar_map.frame is None:
                 raise ValueError(f"{what}: lidar_map must be a LidarMap of this env that keeps a frame")
             frames = lidar_map.frame
+        return frames
+
+    def _nav_launch(self, what: str, margin: int, soft_pen: int, lookahead: int, turn_sin: float,
+                    cost=None, direction=None, target=None, geo_cost=None, cmd=None, tile: Optional[int] = None,
+                    frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False,
+                    lidar_map: Optional["LidarMap"] = None, predict=False) -> None:
+        """One ffmp_nav_field (or, see _nav_tiled, ffmp_nav_field_tiled) launch over the current
+        observation: the newest frame through the window's strides and format, the ego goal from
+        record words 8..9.  frames: plan over this (N, G, G) plane instead of the newest frame;
+        visible: over visible_frames(newest_only=True, unknown=0); lidar: over
+        lidar_frames(newest_only=True, unknown=0); lidar_map: over that LidarMap's frame; predict:
+        over predicted_frames() (True), predicted_frames(**predict) (a dict) or
+        predicted_frames(flow=predict) (a LidarFlow)."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError(f"call reset() before {what}()")
+        frames = self._plane_source(what, frames, visible, lidar, lidar_map, predict)
         obs_c, fmt = self._obs_c, self._fmt
         if frames is not None:
             obs_c = self._nav_plane_obs(frames)
@@ -2060,6 +2088,118 @@ class FFMPVec:
                                                   flow.data_ptr(), flow.stride(0), vfmt, _ptr(mask), out.data_ptr(), G2,
                                                   _ptr(n_swept), *knobs, self._stream()), "ffmp_flow_predict")
         return (out, n_swept) if count else out
+
+    # ------------------------------------------------ potential field of a frame
+    def _potential_reach(self, what: str, reach: Optional[int], exact: bool) -> int:
+        """The window of ffmp_frame_potential in cells: ceil(rho0 / res) by default; a given reach
+        that cuts the repulsive term short of rho0 is refused when the field has to be exact."""
+        need = int(math.ceil(self.cfg.rho0 / self.cfg.res))
+        if reach is None:
+            if need > 32:
+                raise ValueError(f"{what}: rho0 / res = {self.cfg.rho0} / {self.cfg.res} needs a reach of {need} cells, "
+                                 f"above 32 (lower rho0 or raise res)")
+            return need
+        reach = int(reach)
+        if exact and reach < need:
+            raise ValueError(f"{what}: reach = {reach} cells covers {reach * self.cfg.res:.6g} m, short of rho0 = {self.cfg.rho0} "
+                             f"at res = {self.cfg.res} ({need} cells): the potential would be cut off inside rho0 "
+                             f"(potential=False gives the clearance alone at any reach)")
+        return reach
+
+    def _potential_launch(self, plane: Optional[torch.Tensor], goal: Optional[torch.Tensor], occ_min: int, reach: int,
+                          dist2=None, potential=None, grad=None, robot_d2=None, mask=None) -> None:
+        """One ffmp_frame_potential launch on the current stream.  plane: an (N, G, G) float32 or
+        uint8 device tensor whose env planes are dense (None: the newest frame, a view of the
+        window); goal: a contiguous (N, 2) float32 device tensor (None: record words 8..9)."""
+        n, G = self.num_envs, self.cfg.grid
+        fmts = {torch.float32: _abi.OBS_F32, torch.uint8: _abi.OBS_U8F16}
+        if plane is None:
+            plane = self.state_m[:, 1]  # a view: the env stride of the window
+        elif not isinstance(plane, torch.Tensor) or tuple(plane.shape) != (n, G, G) or plane.dtype not in fmts \
+                or not plane.is_contiguous() or plane.device != self.device:
+            raise ValueError(f"frames must be a contiguous float32 or uint8 tensor of shape ({n}, {G}, {G}) on {self.device}")
+        if goal is None:
+            goal_ptr, goal_stride = self.record.data_ptr() + 8 * 4, self.record.stride(0)
+        elif not isinstance(goal, torch.Tensor) or tuple(goal.shape) != (n, 2) or goal.dtype != torch.float32 \
+                or not goal.is_contiguous() or goal.device != self.device:
+            raise ValueError(f"goal must be a contiguous float32 tensor of shape ({n}, 2) on {self.device}")
+        else:
+            goal_ptr, goal_stride = goal.data_ptr(), 2
+        pfmt = _abi.OBS_U8F16 if potential is not None and potential.dtype == torch.float16 else _abi.OBS_F32
+        _abi.check(self.lib.ffmp_frame_potential_check(C.byref(self._cfg_c), fmts[plane.dtype], pfmt, int(occ_min), reach),
+                   "ffmp_frame_potential_check")
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_frame_potential(C.byref(self._cfg_c), n, plane.data_ptr(), plane.stride(0), fmts[plane.dtype],
+                                                     goal_ptr, goal_stride, _ptr(mask), int(occ_min), reach, _ptr(dist2), G * G,
+                                                     _ptr(potential), G * G, pfmt, _ptr(grad), _ptr(robot_d2), self._stream()),
+                       "ffmp_frame_potential")
+
+    def frame_potential(self, frames: Optional[torch.Tensor] = None, visible: bool = False, lidar: bool = False,
+                        lidar_map: Optional["LidarMap"] = None, predict=False, goal: Optional[torch.Tensor] = None,
+                        occ_min: int = 255, reach: Optional[int] = None, distance: bool = False, potential: bool = True,
+                        dtype: torch.dtype = torch.float32, out: Optional[Dict[str, torch.Tensor]] = None,
+                        mask: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The potential field of an occupancy frame, on the device (include/ffmp.h
+        ffmp_frame_potential): what obs["potential"] and obs["grad"] are to the simulator's disc
+        list, for any plane a sensor can give.  Every cell >= `occ_min` is an obstacle (255: hits
+        only, unknown cells do not repel; 1: nav_field's occupancy; a predicted plane marks its
+        swept cells 254).  Returns
+          grad      (N, 2) float32: the central difference of the potential at the robot cell, the
+                    layout policy_field(grad=...) reads
+          robot_d2  (N,) int32: the squared distance in cells from the robot cell to the nearest
+                    obstacle cell within `reach` cells along either axis, -1 when there is none
+          clearance (N,) float64 metres = sqrt(robot_d2) * res, inf where -1
+          potential (N, G, G) `dtype` (float32 or float16) with potential=True: the attractive term of
+                    the raster plus Khatib's repulsive term of the NEAREST obstacle cell — not the sum
+                    over discs of obs["potential"]; walls and anything else in the frame repel
+          dist2     (N, G, G) uint16 with distance=True: the squared clearance of every cell in cells,
+                    65535 where no obstacle lies within the window
+        The plane: the newest frame state_m[:, 1], or one of frames= (a contiguous (N, G, G) float32
+        or uint8 device tensor), visible=True, lidar=True, lidar_map=, predict= as for nav_field.
+        goal: a contiguous (N, 2) float32 device tensor of ego goals instead of the env's own.
+        reach: the window in cells, 1..32; None is ceil(rho0 / res), the smallest at which the field
+        is exact out to rho0 — a smaller one is refused unless potential=False (the clearance alone
+        may use any reach, and `grad` is then of the cut-off field).  out: a dict of tensors to
+        write into, any of "grad", "robot_d2", "potential", "dist2" (contiguous, of the shapes and
+        dtypes above; a plane given there is computed); mask: (N,) bool or uint8, envs with 0 keep
+        every word.  One launch on the current stream, so a caller can capture it into a graph of
+        their own (visible=, lidar= and predict= add theirs); with `out` supplying the planes it
+        allocates only the (N,) clearance.  The step and its observation are untouched."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before frame_potential()")
+        n, G = self.num_envs, self.cfg.grid
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"frame_potential: dtype must be torch.float32 or torch.float16, got {dtype}")
+        out = dict(out) if out else {}
+        unknown = set(out) - {"grad", "robot_d2", "potential", "dist2"}
+        if unknown:
+            raise ValueError(f"frame_potential: out has no plane named {sorted(unknown)}")
+        potential = bool(potential) or "potential" in out
+        distance = bool(distance) or "dist2" in out
+        reach = self._potential_reach("frame_potential", reach, exact=potential)
+        spec = {"grad": ((n, 2), torch.float32), "robot_d2": ((n,), torch.int32)}
+        if potential:
+            spec["potential"] = ((n, G, G), dtype)
+        if distance:
+            spec["dist2"] = ((n, G, G), torch.uint16)
+        res = {}
+        for key, (shape, dt) in spec.items():
+            t = out.get(key)
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            elif not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() \
+                    or t.device != self.device:
+                raise ValueError(f"out[{key!r}] must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+            res[key] = t
+        if mask is not None:
+            mask = torch.as_tensor(mask, device=self.device).reshape(n).to(torch.uint8).contiguous()
+        plane = self._plane_source("frame_potential", frames, visible, lidar, lidar_map, predict)
+        self._potential_launch(plane, goal, occ_min, reach, dist2=res.get("dist2"),
+                               potential=res.get("potential"), grad=res["grad"], robot_d2=res["robot_d2"], mask=mask)
+        rd = res["robot_d2"].to(torch.float64)
+        res["clearance"] = torch.where(rd < 0, torch.full_like(rd, float("inf")), torch.sqrt(rd.clamp(min=0)) * self.cfg.res)
+        return res
 
     def nav_field(self, cost: bool = False, direction: bool = False, margin: int = 2, soft_pen: int = 40,
                   lookahead: int = 4, tile: Optional[int] = None, frames: Optional[torch.Tensor] = None,

@@ -47,6 +47,9 @@
  *                          per-cell velocity by block matching with ego-motion compensation [unpinned]
  *   ffmp_flow_predict   -> what the planner makes of that flow: the frame with the cells a moving
  *                          obstacle will cover when the robot can be there marked occupied [unpinned]
+ *   ffmp_frame_potential -> the potential plane and its gradient (obs.potential, obs.grad) from any of
+ *                          those frames instead of from the simulator's discs, and the clearance
+ *                          plane underneath [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -848,6 +851,62 @@ int ffmp_flow_predict(const ffmp_cfg_t* cfg, int64_t n, const void* frame, int64
                       int32_t swept, int32_t other, void* stream);
 int ffmp_flow_predict_check(const ffmp_cfg_t* cfg, int32_t frame_format, int32_t flow_format, int32_t steps, float cps,
                             int32_t pace, int32_t slack, int32_t swept, int32_t other);
+
+/* Potential field of any occupancy frame (an addition within ABI 9: no existing symbol, struct or value
+ * changes): the clearance plane, the attractive + repulsive potential plane and its gradient at the robot
+ * cell from a frame — state_m's, a visible, scan-built, accumulated or predicted one, or the caller's own —
+ * instead of from the simulator's disc list, so that ffmp_policy_field can follow what a sensor shows.  No
+ * reference counterpart [unpinned]; the SPEC below is the definition.
+ * SPEC, per env.  F: the frame, G x G, row i ego x, column j ego y, c = G/2.  Knobs: occ_min 1..255, reach 1..32.
+ *   obst[a] = F[a] >= occ_min               (a float compare for a float32 frame: a NaN is free)
+ * Clearance, integer arithmetic:
+ *   d2[a] = min of di*di + dj*dj over the obstacle cells b = a + (di, dj) inside the grid with
+ *           |di| <= reach and |dj| <= reach;  65535 if there is none
+ * The window is the square, not the disc: one obstacle at (20, 20) with reach 3 gives d2[23][23] = 18, and
+ * 65535 at (24, 20).  An obstacle cell has d2 = 0.  A minimum is unique, so no order of evaluation shows.
+ * Potential, float32, every expression left to right as written, no contraction, sqrt and the reciprocal
+ * correctly rounded:
+ *   ex = (float)i*res_f - half_f;  ey = (float)j*res_f - half_f
+ *   gx, gy = goal_ego[e*goal_stride + 0..1]
+ *   dx = ex - gx;  dy = ey - gy;  U = half_ka_f * (dx*dx + dy*dy)
+ *   if d2 != 65535:
+ *       d = sqrt((float)d2) * res_f;  d = fmaxf(d, rho_min_f)
+ *       if d < rho0_f:  q = 1.0f/d - inv_rho0_f;  U = U + half_kr_f * (q*q)
+ * The attractive term is the raster's; the repulsive term is Khatib's nearest-obstacle form over the cells of
+ * the frame, deliberately NOT the sum over discs of obs.potential: the two planes differ wherever two
+ * obstacles are within rho0 of a cell, and here the walls and anything else the frame holds repel too.  The
+ * field is exact out to rho0 only if reach * res >= rho0; this entry point does not enforce that (reach is a
+ * knob here; the Python surface enforces it).  A non-finite goal propagates as written: NaN planes and a NaN
+ * gradient, to which ffmp_policy_field answers (0, 0).
+ * potential_format: FFMP_OBS_F32 writes U, FFMP_OBS_U8F16 binary16, round to nearest even from the float32 U
+ * as the compact raster converts.
+ * Gradient, from the float32 U under either format, computed whether or not `potential` is given — the
+ * expression of the env step, the layout ffmp_policy_field reads:
+ *   grad[e] = ((U[c+1][c] - U[c-1][c]) * inv_2res_f, (U[c][c+1] - U[c][c-1]) * inv_2res_f)
+ *   robot_d2[e] = d2[c][c], or -1 where that is 65535
+ * Mask: an env with mask[e] == 0 keeps every output word.
+ * Parity: the kernel equals tests/frame_potential_ref.py bit for bit (NaN payloads aside).
+ * cfg: grid, res_f, half_f, half_ka_f, half_kr_f, rho0_f, inv_rho0_f, rho_min_f and inv_2res_f are read.
+ * frame: DEVICE (n, G, G), env e at e * frame_env_stride elements — a strided view such as state_m[:, 1] of
+ * the ring window passes; frame_format FFMP_OBS_F32: float32, FFMP_OBS_U8F16: uint8.  goal_ego: DEVICE
+ * float32, env e at e * goal_stride (record words 8..9 with the record's stride, or an (n, 2) tensor).
+ * mask: (n) bytes or NULL.  dist2: DEVICE uint16 (n, G, G) or NULL; potential: DEVICE (n, G, G) or NULL;
+ * grad: DEVICE float32 (n, 2) or NULL; robot_d2: DEVICE int32 (n) or NULL.  Every pointer is 4-byte aligned;
+ * env strides count elements, are multiples of 4 and >= G*G.  The frame is read with 16-byte loads where
+ * its base and env stride allow; a lane stores the 4 cells it owns at once (16 bytes of float32, 8 of
+ * binary16 or uint16) where the plane's base allows; 4-byte accesses otherwise.  With both planes NULL only
+ * the rows the gradient needs are worked on.
+ * FFMP_E_ARG, with a message and before any HIP call, for: a grid outside 8..512 or not a multiple of 4; an
+ * unknown format; occ_min outside 1..255; reach outside 1..32; frame or goal_ego NULL; goal_stride < 2; all
+ * four outputs NULL; a stride that is too small or misaligned, or a misaligned base; an output that overlaps
+ * the frame or another output; n < 0 or too large for one launch.  n == 0: nothing is launched.
+ * ffmp_frame_potential_check: the checks that need no pointer (shape, formats, knobs), no launch. */
+int ffmp_frame_potential(const ffmp_cfg_t* cfg, int64_t n, const void* frame, int64_t frame_env_stride, int32_t frame_format,
+                         const float* goal_ego, int64_t goal_stride, const uint8_t* mask, int32_t occ_min, int32_t reach,
+                         uint16_t* dist2, int64_t dist2_env_stride, void* potential, int64_t potential_env_stride,
+                         int32_t potential_format, float* grad, int32_t* robot_d2, void* stream);
+int ffmp_frame_potential_check(const ffmp_cfg_t* cfg, int32_t frame_format, int32_t potential_format, int32_t occ_min,
+                               int32_t reach);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
