@@ -4,6 +4,7 @@ DESIGN §3 a16d) and is tied to the oracle by a closed loop in which it matters;
 ffmp_flow_predict_check are declared, bound and exported consistently inside ABI 9, and every argument check
 answers before any launch."""
 import ctypes as C
+import functools
 import inspect
 import json
 import re
@@ -13,6 +14,7 @@ import pytest
 
 from flow_field_based_motion_planner_amd import _abi
 from flow_field_based_motion_planner_amd.config import FFMPConfig
+from tests import flow_predict_cases as K
 from tests import flow_predict_ref as R
 
 F32 = np.float32
@@ -162,6 +164,96 @@ def test_mask_keeps_a_poisoned_out():
     out, cnt = R.flow_predict(f, flow, steps=4, cps=F32(1.0), mask=np.array([1, 0, 1]), out_in=poison, n_swept_in=np.full(3, -5), **OFF)
     assert (out[1] == 7).all() and cnt.tolist() == [4, -5, 4] and cnt.dtype == np.int32
     assert np.array_equal(out[0], out[2]) and _cells(out[0], 254) == [(i, 20) for i in range(21, 25)]
+
+
+# ------------------------------------------------------------------ 4b. the GPU ladder's cases show what they are for
+def _edges(sw):
+    """Swept cells of (n, G, G) in the first 8 rows, the last 8 rows, the first 8 columns, the last 8 columns: (n, 4)."""
+    return np.stack([sw[:, :8].sum(axis=(1, 2)), sw[:, -8:].sum(axis=(1, 2)), sw[:, :, :8].sum(axis=(1, 2)),
+                     sw[:, :, -8:].sum(axis=(1, 2))], axis=1)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(G, n, which, ft, vt, knob):
+    """(swept mask, n_swept) of a ladder case in one format pair: computed once per session."""
+    f, v = K.cast(*K.case_planes(G, n, which), ft, vt)
+    out, cnt = R.flow_predict(f, v, **dict(K.KNOBS, **K.knobs(knob, G)))
+    assert cnt.sum() == (out == 254).sum()
+    return out == 254, cnt
+
+
+LADDER_CASES = [(G, n, knob, which, fmts) for knob, which, fmts, sizes in K.GPU_LADDER for G, n in K.LADDER if G in sizes]
+LADDER_CASES.append(K.MANY + ("open", "overflow", K.ENDS[1:]))
+LADDER_CASES += [(G, n, "open", "overflow", K.ENDS) for G, n in K.CORRECTED]
+
+
+@pytest.mark.parametrize("G,n,knob,which,fmts", LADDER_CASES, ids=lambda v: v if isinstance(v, (int, str)) else str(len(v)))
+def test_ladder_cases_put_bits_where_they_are_meant_to(G, n, knob, which, fmts):
+    """Conditions on the restatement's output for every (G, knob set, density, format pair) that
+    tests/test_gpu_flow_predict.py runs.  Not measurements: a generator that misses one gets another seed or
+    density.  Measured with these planes, per case and format pair: open, the fewest swept cells in an 8-cell edge
+    band of one env 438 on overflow and 19 on listed, the last 16 flat cells hit at every size; far gate, 384 or
+    more swept cells per edge band of a case on overflow and 21 or more on listed, gated / open counts 0.23 to 0.39;
+    moving sources per env 1,427 to 7,744 on overflow and 290 to 744 on listed."""
+    for ft, vt in fmts:
+        f, v = K.cast(*K.case_planes(G, n, which), ft, vt)
+        moving = K.moving_sources(f, v)
+        assert ((moving < K.LIST) if which == "listed" else (moving > K.LIST)).all(), (ft, vt, moving)
+        sw, cnt = _restated(G, n, which, ft, vt, knob)
+        edges = _edges(sw)
+        if knob == "open":
+            assert (edges > 0).all(), (ft, vt, edges)
+            assert sw.reshape(n, -1)[:, -16:].any(), (ft, vt)
+        elif knob == "far":
+            assert (edges.sum(axis=0) > 0).all(), (ft, vt, edges)
+            wide = _restated(G, n, which, ft, vt, "open")[1].sum()
+            assert 0 < cnt.sum() < wide, (ft, vt, cnt.sum(), wide)
+        else:  # default: why the other two exist
+            assert G >= 128 and cnt.sum() > 0 and (edges == 0).all(), (ft, vt, edges)
+
+
+@pytest.mark.parametrize("G,n", [s for s in K.LADDER if s[0] >= 128])
+def test_default_knobs_reach_no_border_at_the_benchmark_grids_and_above(G, n):
+    f, v = K.cast(*K.case_planes(G, n, "overflow"), np.float32, np.float32)
+    out, cnt = R.flow_predict(f, v, **K.KNOBS)
+    assert cnt.sum() > 0 and not _edges(out == 254).any()
+    ii = np.nonzero(out == 254)
+    assert max(np.abs(ii[1] - G // 2).max(), np.abs(ii[2] - G // 2).max()) <= 33  # (5 * 33) // 6 = 27 = steps + slack
+
+
+def test_the_row_correction_runs_only_at_the_sizes_chosen_for_it():
+    """pred_walk recovers the row of a flat cell as (int)((float)q * (1.0f / G)) and corrects it by one either way.
+    Restated in float32: the correction downwards is never needed, the one upwards at 15 grids, none of them on the
+    ladder; K.CORRECTED holds two, and their planes have moving sources on such cells in every env — sources that
+    a kernel without the correction would walk from column G of the row above."""
+    needing = {}
+    for G in range(8, 516, 4):
+        high, low = K.uncorrected_cells(G)
+        assert not len(high), G
+        if len(low):
+            assert (low % G == 0).all()
+            needing[G] = len(low)
+    assert sorted(needing) == [164, 188, 220, 244, 328, 332, 376, 388, 428, 436, 440, 460, 484, 488, 492]
+    assert not set(needing) & set(K.SIZES)
+    for G, n in K.CORRECTED:
+        assert needing[G] > 200 and (K.lds_bytes(G) > 65536) == (G == 460)
+        for ft, vt in K.ENDS:
+            f, v = K.cast(*K.case_planes(G, n, "overflow"), ft, vt)
+            with np.errstate(all="ignore"):
+                su, sv = v[:, 0].astype(F32) * K.KNOBS["cps"], v[:, 1].astype(F32) * K.KNOBS["cps"]
+                moving = (f == 255) & np.isfinite(su) & np.isfinite(sv) & ~((su == 0) & (sv == 0))
+            on = moving.reshape(n, -1)[:, K.uncorrected_cells(G)[1]].sum(axis=1)
+            assert (on >= 20).all(), (G, ft, vt, on)
+
+
+def test_ladder_sizes_sit_on_both_sides_of_the_lds_cap():
+    assert [K.lds_bytes(g) for g in (404, 408, 508, 512)] == [65304, 66520, 100872, 102400]
+    assert K.lds_bytes(404) <= 65536 < K.lds_bytes(408) and [g * g % 32 for g in (100, 260, 404, 508)] == [16] * 4
+    assert K.knobs("far", 512)["pace"] == 28 and K.knobs("far", 100)["pace"] == 6
+    # the moved generator at its default density is the one the earlier random test used
+    a = K.planes(100, 3, seed=103)
+    b = K.planes(100, 3, seed=103, density=0.03)
+    assert all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b)) and K.moving_sources(*a).max() < K.LIST
 
 
 # ------------------------------------------------------------------ 5. the C surface and its refusals

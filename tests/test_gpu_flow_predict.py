@@ -6,12 +6,22 @@ their NumPy restatement (tests/flow_predict_ref.py), bit for bit:
    plane whose every cell is a source;
 2. the corners of the knobs;
 3. mask=, env strides of a larger buffer, and bases aligned to 4 but not 16 bytes (the 4-byte loads and stores);
+3b. the size ladder of tests/flow_predict_cases.py — G = 100, 128, 256, 260, 404, 408, 508, 512: both benchmark
+   grids, both sides of the 64 KiB cap of dynamic LDS, the half-used last bit word — with the gate off and with a
+   gate that reaches the border, below and above 1,024 moving sources per env (gate off and above in the four
+   formats, the rest in float32 / float32 and uint8 / binary16); the default knobs at 256 and 512; 256 with n = 70;
+   244 and 460, where pred_walk's row correction runs; the 4-byte paths at 408; mask= at 512.
+   tests/test_flow_predict_host.py proves on the restatement that these cases sweep the borders and the last word;
 4. FFMPVec.predicted_frames over the env's own frame and flow and over a LidarFlow, nav_field / policy_nav
-   with predict=, the errors;
+   with predict=, the errors; the surface on live envs at G = 256 (untiled planner) and 260 (tiled);
 5. the crossing family in closed loop: the outcomes of the CPU run, scene by scene and step by step;
-6. inside a graph capture of the caller's."""
+6. inside a graph capture of the caller's; in a fresh process (tests/first_capture_child.py), the first launch above
+   64 KiB of LDS made while capturing, for ffmp_flow_predict, ffmp_frame_potential and ffmp_scan_flow."""
 import ctypes as C
 import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -21,6 +31,7 @@ from flow_field_based_motion_planner_amd import _abi
 from flow_field_based_motion_planner_amd.config import FFMPConfig
 from flow_field_based_motion_planner_amd.env import FFMP
 from flow_field_based_motion_planner_amd.vec_env import FFMPVec
+from tests import flow_predict_cases as K
 from tests import flow_predict_ref as R
 from tests import nav_field_ref as NR
 from tests.scan_flow_ref import TIE
@@ -28,40 +39,12 @@ from tests.scan_flow_ref import TIE
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F32 = np.float32
-KNOBS = dict(steps=24, cps=F32(2.0), pace=6, slack=3, swept=254, other=128)
-FORMATS = [(np.float32, np.float32), (np.float32, np.float16), (np.uint8, np.float32), (np.uint8, np.float16)]
+KNOBS, FORMATS = K.KNOBS, K.FORMATS
+_planes = K.planes
 
 
 def _t(x):
     return torch.as_tensor(np.ascontiguousarray(x), device=DEV)
-
-
-def _planes(G, n, seed, cps=2.0, dense=False):
-    """(frame float32 with values a uint8 holds, flow float32): about 3 % sources and 3 % other occupied cells, flows
-    within +-2 cells per step, special values sprinkled over the flow, outward sources on the borders."""
-    rng = np.random.default_rng(seed)
-    u = rng.random((n, G, G))
-    frame = np.zeros((n, G, G), F32)
-    frame[u < 0.03] = 255
-    other = (u >= 0.03) & (u < 0.06)
-    frame[other] = rng.integers(1, 255, int(other.sum()))
-    if dense:
-        frame[:] = 255
-    flow = (rng.uniform(-2.0, 2.0, (n, 2, G, G)) / cps).astype(F32)
-    # the borders: every fourth cell a source that points outward (and sideways)
-    frame[:, 0, ::4] = frame[:, G - 1, 1::4] = frame[:, 2::4, 0] = frame[:, 3::4, G - 1] = 255
-    flow[:, 0, 0, ::4] = -np.abs(flow[:, 0, 0, ::4]) - F32(0.3)
-    flow[:, 0, G - 1, 1::4] = np.abs(flow[:, 0, G - 1, 1::4]) + F32(0.3)
-    flow[:, 1, 2::4, 0] = -np.abs(flow[:, 1, 2::4, 0]) - F32(0.3)
-    flow[:, 1, 3::4, G - 1] = np.abs(flow[:, 1, 3::4, G - 1]) + F32(0.3)
-    s = rng.random((n, 2, G, G))
-    flow[s < 0.01] = np.nan
-    flow[(s >= 0.01) & (s < 0.02)] = np.inf
-    flow[(s >= 0.02) & (s < 0.03)] = -np.inf
-    flow[(s >= 0.03) & (s < 0.06)] = -0.0
-    flow[(s >= 0.06) & (s < 0.08)] = 0.0
-    flow[(s >= 0.08) & (s < 0.09)] = 3e38
-    return frame, flow
 
 
 def _cfg(G):
@@ -205,6 +188,80 @@ def test_mask_strides_and_unaligned_bases(lib):
     assert (out == 7).all()
 
 
+# ------------------------------------------------------------------ 3b. the size ladder (tests/flow_predict_cases.py)
+def _ladder(lib, G, n, knob, which, fmts):
+    """A ladder case in the given format pairs against the restatement; tests/test_flow_predict_host.py holds the proof
+    that the case puts bits at the borders, in the last word and on the stated side of the list."""
+    frame, flow = K.case_planes(G, n, which)
+    for ft, vt in fmts:
+        f, v = K.cast(frame, flow, ft, vt)
+        exp, cnt = _run(lib, G, f, v, ft, vt, (G, n, knob, which, ft.__name__, vt.__name__), **K.knobs(knob, G))
+        assert cnt.sum() == (exp == 254).sum() and cnt.sum() > 0
+
+
+@pytest.mark.parametrize("G,n", K.LADDER)
+@pytest.mark.parametrize("knob,which,fmts", [c[:3] for c in K.GPU_LADDER[:4]], ids=lambda v: v if isinstance(v, str) else str(len(v)))
+def test_ladder_equals_the_restatement(lib, G, n, knob, which, fmts):
+    _ladder(lib, G, n, knob, which, fmts)
+
+
+@pytest.mark.parametrize("G", K.GPU_LADDER[4][3])
+def test_ladder_default_knobs_at_the_timed_grids(lib, G):
+    knob, which, fmts, _ = K.GPU_LADDER[4]
+    _ladder(lib, G, dict(K.LADDER)[G], knob, which, fmts)
+
+
+def test_ladder_many_envs_at_256(lib):
+    _ladder(lib, *K.MANY, "open", "overflow", K.ENDS[1:])
+
+
+@pytest.mark.parametrize("G,n", K.CORRECTED)
+def test_sizes_at_which_the_row_correction_runs(lib, G, n):
+    """No ladder size makes pred_walk's float quotient miss the row (tests/test_flow_predict_host.py); these two do."""
+    _ladder(lib, G, n, "open", "overflow", K.ENDS)
+
+
+def test_unaligned_bases_and_padded_strides_at_408(lib):
+    """The 4-byte loads and stores on the opt-in branch: bases at 4 mod 16 bytes, env strides of G*G + 4 elements."""
+    G, n = 408, 2
+    G2 = G * G
+    frame, flow = K.case_planes(G, n, "overflow")
+    knobs = K.knobs("open", G)
+    for ft, vt in K.ENDS:
+        fc, vc = K.cast(frame, flow, ft, vt)
+        exp, cnt = R.flow_predict(fc, vc, **dict(KNOBS, **knobs))
+        fe = 4 // np.dtype(ft).itemsize  # elements in 4 bytes
+        fbuf = torch.zeros(n * (G2 + 4) + fe, dtype=torch.float32 if ft is np.float32 else torch.uint8, device=DEV)
+        fv = fbuf[fe:].reshape(n, G2 + 4)
+        fv[:, :G2] = _t(fc).reshape(n, G2)
+        ve = 4 // np.dtype(vt).itemsize
+        vbuf = torch.zeros(n * (2 * G2 + 4) + ve, dtype=torch.float32 if vt is np.float32 else torch.float16, device=DEV)
+        vv = vbuf[ve:].reshape(n, 2 * G2 + 4)
+        vv[:, :2 * G2] = _t(vc).reshape(n, 2 * G2)
+        obuf = torch.full((n * (G2 + 4) + 4,), 7, dtype=torch.uint8, device=DEV)
+        ov = obuf[4:].reshape(n, G2 + 4)
+        n_swept = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+        assert fv.data_ptr() % 16 == 4 and vv.data_ptr() % 16 == 4 and ov.data_ptr() % 16 == 4
+        _launch(lib, G, fv, vv, ov, n_swept, **knobs)
+        _same(ov[:, :G2].reshape(n, G, G), exp, ("unaligned 408", ft.__name__, vt.__name__))
+        _same(n_swept, cnt, ("unaligned 408 n_swept", ft.__name__, vt.__name__))
+        assert (ov[:, G2:] == 7).all() and (obuf[:4] == 7).all()
+        assert cnt.sum() == (exp == 254).sum() and cnt.sum() > 0
+
+
+def test_mask_at_512(lib):
+    G, n = 512, 2
+    frame, flow = K.cast(*K.case_planes(G, n, "overflow"), np.float32, np.float32)
+    knobs = K.knobs("open", G)
+    exp, cnt = R.flow_predict(frame, flow, **dict(KNOBS, **knobs))
+    out = torch.full((n, G, G), 7, dtype=torch.uint8, device=DEV)
+    n_swept = torch.full((n,), -9, dtype=torch.int32, device=DEV)
+    _launch(lib, G, _t(frame), _t(flow), out, n_swept, mask=_t(np.array([1, 0], np.uint8)), **knobs)
+    _same(out[0], exp[0], "mask 512, env 0")
+    assert (out[1] == 7).all() and n_swept.tolist() == [int(cnt[0]), -9]
+    assert cnt[0] == (exp[0] == 254).sum() and cnt[0] > 0
+
+
 # ------------------------------------------------------------------ 4. FFMPVec
 def _expect(env, frame=None, flow=None, **kw):
     cps, pace = R.host_knobs(kw.pop("dt", env.cfg.dt), env.cfg.res, kw.pop("speed", 0.6))
@@ -292,6 +349,38 @@ def test_predicted_frames_of_a_live_env(fmt):
     env.close()
 
 
+@pytest.mark.parametrize("fmt", ["f32", "u8f16"])
+@pytest.mark.parametrize("G", [256, 260])
+def test_predicted_frames_at_the_benchmark_grid_and_above(G, fmt):
+    """C3's grid, where the planner holds the plane in LDS, and 256 + 4, where it goes through ffmp_nav_field_tiled:
+    the surface over a real frame ring's strides, the far-reaching call, and the planner over the predicted plane."""
+    cfg = FFMPConfig(grid=G, n_obst=12, n_beams=0, moving=True, flow=True, world_half=3.0, goal_min=1.0, goal_max=3.5,
+                     obst_rmax=0.6, obst_vmax=1.0, max_steps=50, seed=8)
+    n = 2
+    env = FFMPVec(n, cfg, device=DEV, autotune=False, obs_format=fmt)
+    env.reset()
+    for a in (24, 3, 25):
+        env.step(torch.full((n,), a, dtype=torch.int64, device=DEV))
+    assert (env._nav_tiled(None) is not None) == (G > 256)
+    exp, cnt = _expect(env)
+    assert cnt.sum() > 0
+    _same(env.predicted_frames(), exp, (G, fmt, "own flow"))
+    got, n_swept = env.predicted_frames(count=True)
+    _same(got, exp, (G, fmt, "count=True"))
+    _same(n_swept, cnt, (G, fmt, "count"))
+    far, far_cnt = _expect(env, slack=-1, steps=64)
+    assert far_cnt.sum() > cnt.sum()
+    got_far, n_far = env.predicted_frames(slack=-1, steps=64, count=True)
+    _same(got_far, far, (G, fmt, "gate off, 64 steps"))
+    _same(n_far, far_cnt, (G, fmt, "gate off, 64 steps, count"))
+    goals = env.record[:, 8:10].cpu().numpy()
+    _same(env.policy_nav(predict=True), NR.nav_field(exp, goals, cfg)["cmd"], (G, fmt, "policy_nav(predict=True)"))
+    for kw, plane in ((dict(predict=True), got), (dict(predict=dict(slack=-1, steps=64)), got_far)):
+        a, b = env.nav_field(cost=True, **kw), env.nav_field(cost=True, frames=plane)
+        assert all(torch.equal(a[k], b[k]) for k in ("cost", "target", "geo_cost")), (G, fmt, kw)
+    env.close()
+
+
 def test_without_flow_planes_and_the_single_env():
     cfg = FFMPConfig(grid=64, n_obst=4, n_beams=0, moving=True)
     env = FFMPVec(2, cfg, device=DEV, autotune=False)
@@ -351,6 +440,19 @@ def test_crossing_family_equals_the_cpu_closed_loop():
 
 
 # ------------------------------------------------------------------ 6. inside a graph capture
+def test_first_opt_in_launch_of_a_process_inside_a_capture():
+    """tests/first_capture_child.py in a fresh process: for ffmp_flow_predict, ffmp_frame_potential and ffmp_scan_flow
+    the first call of the process above 64 KiB of dynamic LDS (grid 512) is made while a stream is capturing, and the
+    replay equals the restatement.  One child, no retries: a non-zero exit or the time limit is the failure."""
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "first_capture_child.py")
+    done = subprocess.run([sys.executable, child], capture_output=True, text=True, timeout=120)
+    print(done.stdout, done.stderr)
+    assert done.returncode == 0, (done.returncode, done.stdout[-2000:], done.stderr[-2000:])
+    seen = [json.loads(line) for line in done.stdout.splitlines() if line.startswith("{")]
+    assert [(r["pass"], r["outcome"]) for r in seen] == [("ffmp_flow_predict", "match"), ("ffmp_frame_potential", "match"),
+                                                        ("ffmp_scan_flow", "match")], seen
+
+
 def test_graph_capture():
     cfg = FFMPConfig(**TIE[64])
     n = 4
