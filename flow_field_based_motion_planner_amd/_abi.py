@@ -169,6 +169,10 @@ _SIGS = {
     "ffmp_frame_potential": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _I64, _P, _I32, _I32, _P, _I64, _P, _I64, _I32,
                                        _P, _P, _P]),
     "ffmp_frame_potential_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32]),
+    # the rollout (dynamic-window) planner over a cost plane and a flow (an addition within ABI 9)
+    "ffmp_dwa": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _I64, _I32, _P, _I64, _I32, C.c_float, _I32, _P, _P, _I32, _I32,
+                           _P, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    "ffmp_dwa_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, C.c_float, _I32, _I32, _I32, C.c_double, C.c_double]),
     "ffmp_reward_done": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I32, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "ffmp_footprint_collision": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _P]),

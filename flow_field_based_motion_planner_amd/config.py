@@ -37,6 +37,69 @@ def action_table() -> List[Tuple[float, float]]:
     return [(v, w) for v in CMD_V for w in CMD_W]
 
 
+ROLLOUT_MAX = 28  # |cell offset| a rollout table may hold (include/ffmp.h ffmp_dwa: 28 + 3 footprint cells = 31)
+
+
+def _rollouts(cfg, v, w, horizon: int, stride: int, probe: float):
+    """The unicycle (DESIGN §3 "Unicycle") rolled forward from ego pose (0, 0, 0) per candidate
+    m = len(w) * vi + wi, float64 with math.cos / math.sin: (cells (A, H, 2), probes (A, H, 2), cmds (A, 2)) —
+    cells[m][k-1] the cell offset after k * stride env steps, probes[m][k-1] that of the point `probe` metres
+    ahead of it along the heading at that moment."""
+    horizon, stride, probe = int(horizon), int(stride), float(probe)
+    if horizon < 1 or stride < 1:
+        raise ValueError(f"rollout_table: horizon and stride must be >= 1, got {horizon}, {stride}")
+    if not (math.isfinite(probe) and probe >= 0):
+        raise ValueError(f"rollout_table: probe must be finite and >= 0, got {probe}")
+    v, w = [float(a) for a in v], [float(a) for a in w]
+    if not v or not w or not all(math.isfinite(a) for a in v + w):
+        raise ValueError("rollout_table: v and w must be non-empty lists of finite numbers")
+    res, dt = float(cfg.res), float(cfg.dt)
+    cmds = np.array([(vm, wm) for vm in v for wm in w], dtype=np.float64)
+    cells = np.zeros((len(cmds), horizon, 2), dtype=np.float64)
+    probes = np.zeros_like(cells)
+    for m, (vm, wm) in enumerate(cmds.tolist()):
+        x = y = yaw = 0.0
+        for k in range(1, horizon + 1):
+            for _ in range(stride):
+                x += (vm * math.cos(yaw)) * dt
+                y += (vm * math.sin(yaw)) * dt
+                yaw += wm * dt
+            cells[m, k - 1] = (x / res, y / res)
+            probes[m, k - 1] = ((x + probe * math.cos(yaw)) / res, (y + probe * math.sin(yaw)) / res)
+    return np.rint(cells), np.rint(probes), cmds
+
+
+def rollout_table(cfg, v=(0, .2, .4, .6), w=(-.6, -.4, -.2, 0, .2, .4, .6), horizon: int = 24, stride: int = 1,
+                  probe: float = 0.325):
+    """The candidate table of the rollout planner (include/ffmp.h ffmp_dwa): (traj int16 (A, H + 1, 2),
+    cmds float64 (A, 2)).  Candidate m = len(w) * vi + wi is the command (v[vi], w[wi]) — with the default
+    lists the reference's action id (RobotAction.cmd, config.py:28-55).  traj[m][k-1], k = 1..H, is the cell
+    offset (rint(x / res), rint(y / res)) of the unicycle after k * stride env steps of that command from ego
+    pose (0, 0, 0); traj[m][H] is the probe, the endpoint pushed `probe` metres forward along the final
+    heading (the forward point of ROS's dwa_local_planner: what lets a turn on the spot score a heading).
+    All trigonometry is here, float64; the kernel sees integers.  ValueError if any |offset| exceeds 28
+    (ROLLOUT_MAX) — at res 0.05, dt 0.1 the default lists fit up to horizon 18 (rollout_horizon)."""
+    cells, probes, cmds = _rollouts(cfg, v, w, horizon, stride, probe)
+    traj = np.concatenate([cells, probes[:, -1:]], axis=1)
+    worst = float(np.abs(traj).max())
+    if not worst <= ROLLOUT_MAX:  # a NaN (res or dt of 0) fails too
+        raise ValueError(f"rollout_table: a rollout reaches {worst:.0f} cells from the robot, more than {ROLLOUT_MAX} "
+                         f"(horizon {horizon}, stride {stride}, probe {probe}, dt {cfg.dt}, res {cfg.res}): shorten it")
+    return traj.astype(np.int16), cmds
+
+
+def rollout_horizon(cfg, v=(0, .2, .4, .6), w=(-.6, -.4, -.2, 0, .2, .4, .6), horizon: int = 24, stride: int = 1,
+                    probe: float = 0.325) -> int:
+    """The longest horizon H <= `horizon` at which rollout_table(cfg, v, w, H, stride, probe) stays within
+    its 28 cells; ValueError if not even H = 1 does."""
+    cells, probes, _ = _rollouts(cfg, v, w, horizon, stride, probe)
+    for H in range(int(horizon), 0, -1):
+        if max(np.abs(cells[:, :H]).max(), np.abs(probes[:, H - 1]).max()) <= ROLLOUT_MAX:
+            return H
+    raise ValueError(f"rollout_horizon: no horizon keeps the rollouts within {ROLLOUT_MAX} cells "
+                     f"(stride {stride}, probe {probe}, dt {cfg.dt}, res {cfg.res})")
+
+
 def footprint_offsets(grid: int, res: float = 0.05, robot_r: float = 0.13) -> List[Tuple[int, int]]:
     """robot_grids of FFMP.is_collision (ffmp.py:87-94), generalised to any G.
 

@@ -425,6 +425,14 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before predicted_frames()")
         return self._vec_env().predicted_frames(**kw)
 
+    def policy_dwa(self, **kw):
+        """The rollout planner's next command for this one env (FFMPVec.policy_dwa, include/ffmp.h
+        ffmp_dwa): a device tensor (1, 2) float64 — (1,) int64 action ids with actions=True, the dict
+        of device tensors with detail=True."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before policy_dwa()")
+        return self._vec_env().policy_dwa(**kw)
+
     def frame_potential(self, **kw):
         """The potential field of an occupancy frame of this one env (FFMPVec.frame_potential,
         include/ffmp.h ffmp_frame_potential): a dict of device tensors with a leading 1 — grad (1, 2),

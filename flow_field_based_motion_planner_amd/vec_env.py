@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .config import PRESETS, FFMPConfig, beam_table, preset, sector_table
+from .config import PRESETS, FFMPConfig, beam_table, preset, rollout_horizon, rollout_table, sector_table
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -2282,6 +2282,131 @@ class FFMPVec:
                          visible=visible, lidar=lidar, lidar_map=lidar_map, predict=predict)
         return out
 
+    # ------------------------------------------------ the rollout planner
+    DWA_STOP = 3       # the action id of the command (0, 0): what actions=True answers when nothing is admissible
+    DWA_SPEED = 0.5    # m/s, the sampler's top obstacle speed: what the default src_reach allows for
+    _dwa_tables = None  # (horizon, stride, probe) -> (H, traj, cmds) on the device
+    _dwa_cost = None    # the cost plane between the two launches, kept from call to call
+
+    def _dwa_table(self, horizon: int, stride: int, probe: float):
+        """The device copy of config.rollout_table for this config, cut to the longest horizon <= `horizon`
+        that keeps the table within its 28 cells (config.rollout_horizon); made once per
+        (horizon, stride, probe) and dropped when the config changes."""
+        key = (int(horizon), int(stride), float(probe))
+        if self._dwa_tables is None:
+            self._dwa_tables = {}
+        t = self._dwa_tables.get(key)
+        if t is None:
+            H = rollout_horizon(self.cfg, horizon=key[0], stride=key[1], probe=key[2])
+            traj, cmds = rollout_table(self.cfg, horizon=H, stride=key[1], probe=key[2])
+            t = self._dwa_tables[key] = (H, torch.as_tensor(traj, device=self.device), torch.as_tensor(cmds, device=self.device))
+        return t
+
+    def policy_dwa(self, out: Optional[torch.Tensor] = None, horizon: int = 24, stride: int = 1, probe: float = 0.325,
+                   flow=True, vel: Optional[torch.Tensor] = None, accel=None, src_reach: Optional[int] = None,
+                   actions: bool = False, detail: bool = False, margin: int = 2, soft_pen: int = 40,
+                   tile: Optional[int] = None, frames: Optional[torch.Tensor] = None, visible: bool = False,
+                   lidar: bool = False, lidar_map: Optional["LidarMap"] = None):
+        """The next (v, w) commands (N, 2) float64 from a dynamic-window / trajectory-rollout planner, on the
+        device (include/ffmp.h ffmp_dwa): the reference's 28 commands (4 speeds x 7 turn rates) are each rolled
+        forward through the robot's own unicycle for up to `horizon` steps of `stride` env steps, rejected
+        where they leave the grid, stand on a hard cell of the navigation field, or meet a moving obstacle AT THE
+        STEP the robot is there (every 255 cell with a velocity moved along it, step by step, against the
+        robot's footprint), and the admissible one that ends lowest on the field — cost at the endpoint plus
+        cost at the probe, the point `probe` metres ahead of it along the final heading — is chosen; (0, 0)
+        when none is admissible.  Two launches: nav_field's (cost=True, with `margin`, `soft_pen`, `tile`, and
+        `frames` / `visible` / `lidar` / `lidar_map` by nav_field's conventions) and ffmp_dwa's.
+        horizon: an upper bound — the table holds cell offsets of at most 28, so the rollouts are cut to the
+        longest horizon that fits (config.rollout_horizon: 18 at res 0.05, dt 0.1; detail=True reports it).
+        flow: True — the env's own flow planes over the newest frame (ValueError if the env was made without
+        flow=True); None or False — static only; a LidarFlow of this env — its estimate over its frame.
+        src_reach: moving sources are looked for within this many cells of the robot (per axis); default
+        min(G // 2, 31 + ceil(H * cps * 0.5)) with cps = float32(stride * dt / res) — what an obstacle at the
+        sampler's top speed of 0.5 m/s can bring into the rollouts' 31 cells within the horizon.
+        accel=(dv_max, dw_max) with vel, a contiguous (N, 2) float64 device tensor of the robot's present
+        (v, w): only the commands within that window of it are candidates (the dynamic window).
+        out: write the commands into this (N, 2) float64 tensor (e.g. command_buffer).  actions=True: return
+        (N,) int64 action ids instead — the candidate number is the reference's action id; id 3 = (0, 0) when
+        none is admissible.  detail=True: a dict with cmd, action, choice (N,) int32 (-1: none), score (N,)
+        uint32 (0xFFFFFFFF: none), n_adm (N,) int32, blocked_at (N, 28) uint8 (the first blocked step per
+        candidate, horizon + 1 if free, 0 outside the window), cost (N, G, G) uint16 and horizon.
+        Known limits: present occupancy stays hard at every step (the cost plane holds it); constant-velocity
+        prediction; nothing is checked between successive steps; the candidate set is discrete.  Inside a
+        graph capture of the caller's: call it once eagerly first with the same arguments (the table is
+        copied to the device, and nav_field's workspace made, at the first call)."""
+        self._check_open()
+        if self._needs_reset:
+            raise RuntimeError("call reset() before policy_dwa()")
+        n, G = self.num_envs, self.cfg.grid
+        if isinstance(flow, LidarFlow):
+            if flow.env is not self:
+                raise ValueError("policy_dwa: flow must be a LidarFlow of this env")
+            src, vflow = flow.frame, flow.flow
+        elif flow is True:
+            if self.flow is None:
+                raise ValueError("policy_dwa: the env was made without flow=True; pass flow=None (static only) or a LidarFlow")
+            src, vflow = self.state_m[:, 1], self.flow  # a view: the env stride of the window
+        elif flow is None or flow is False:
+            src = vflow = None
+        else:
+            raise ValueError("policy_dwa: flow must be True, None / False or a LidarFlow of this env")
+        if (vel is None) != (accel is None):
+            raise ValueError("policy_dwa: vel and accel=(dv_max, dw_max) go together")
+        dv_max = dw_max = 0.0
+        if vel is not None:
+            if not isinstance(vel, torch.Tensor) or tuple(vel.shape) != (n, 2) or vel.dtype != torch.float64 \
+                    or not vel.is_contiguous() or vel.device != self.device:
+                raise ValueError(f"vel must be a contiguous float64 tensor of shape ({n}, 2) on {self.device}")
+            dv_max, dw_max = (float(a) for a in accel)
+        if actions:
+            if out is not None and (tuple(out.shape) != (n,) or out.dtype != torch.int64 or not out.is_contiguous()
+                                    or out.device != self.device):
+                raise ValueError(f"out must be a contiguous int64 tensor of shape ({n},) on {self.device} with actions=True")
+            ids, out = out, None
+        if out is None:
+            out = torch.empty((n, 2), dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (n, 2) or out.dtype != torch.float64 or not out.is_contiguous() \
+                or out.device != self.device or out.data_ptr() % 16:
+            raise ValueError(f"out must be a contiguous, 16-byte aligned float64 tensor of shape ({n}, 2) on {self.device}")
+        H, traj, cmds = self._dwa_table(horizon, stride, probe)
+        A = int(cmds.shape[0])
+        cps = float(np.float32(int(stride) * self.cfg.dt / self.cfg.res))
+        if src_reach is None:
+            src_reach = min(G // 2, 31 + int(math.ceil(H * cps * self.DWA_SPEED)))
+        fmts = {torch.float32: _abi.OBS_F32, torch.uint8: _abi.OBS_U8F16}
+        ffmt = fmts[src.dtype] if src is not None else _abi.OBS_F32
+        vfmt = _abi.OBS_U8F16 if vflow is not None and vflow.dtype == torch.float16 else _abi.OBS_F32
+        _abi.check(self.lib.ffmp_dwa_check(C.byref(self._cfg_c), ffmt, vfmt, cps, int(src_reach), A, H, dv_max, dw_max),
+                   "ffmp_dwa_check")
+        if detail or self._dwa_cost is None or tuple(self._dwa_cost.shape) != (n, G, G):
+            cost = torch.empty((n, G, G), dtype=torch.uint16, device=self.device)
+            if not detail:
+                self._dwa_cost = cost
+        else:
+            cost = self._dwa_cost
+        self._nav_launch("policy_dwa", margin, soft_pen, self.NAV_DEFAULTS["lookahead"], self.NAV_DEFAULTS["turn_sin"],
+                         cost=cost, tile=tile, frames=frames, visible=visible, lidar=lidar, lidar_map=lidar_map)
+        choice = torch.empty(n, dtype=torch.int32, device=self.device) if actions or detail else None
+        more = {}
+        if detail:
+            more = dict(score=torch.empty(n, dtype=torch.uint32, device=self.device),
+                        n_adm=torch.empty(n, dtype=torch.int32, device=self.device),
+                        blocked_at=torch.empty((n, A), dtype=torch.uint8, device=self.device))
+        with torch.cuda.device(self.device):
+            _abi.check(self.lib.ffmp_dwa(C.byref(self._cfg_c), n, cost.data_ptr(), G * G, _ptr(src),
+                                         src.stride(0) if src is not None else 0, ffmt, _ptr(vflow),
+                                         vflow.stride(0) if vflow is not None else 0, vfmt, cps, int(src_reach),
+                                         traj.data_ptr(), cmds.data_ptr(), A, H, _ptr(vel), dv_max, dw_max, None,
+                                         _ptr(choice), out.data_ptr(), _ptr(more.get("score")), _ptr(more.get("n_adm")),
+                                         _ptr(more.get("blocked_at")), self._stream()), "ffmp_dwa")
+        if actions or detail:
+            act = torch.where(choice < 0, torch.full_like(choice, self.DWA_STOP), choice).to(torch.int64)
+            if actions and ids is not None:
+                act = ids.copy_(act)
+        if detail:
+            return dict(more, cmd=out, action=act, choice=choice, cost=cost, horizon=H)
+        return act if actions else out
+
     # ------------------------------------------------ HIP graph of whole steps
     def graph_period(self) -> int:
         """Steps after which the frame pair is back on the same ring slots (so one captured
@@ -2405,6 +2530,7 @@ class FFMPVec:
         self.cfg = cfg
         self._cfg_c = _abi.make_cfg(self.cfg, _ptr(self.beam_cs) or 0)
         self._cfg_gen += 1
+        self._dwa_tables = None  # rollout tables hold the old config's dt and res
         if self._graphs is not None:
             self._graphs = {}
 
@@ -2436,6 +2562,7 @@ class FFMPVec:
         self._arena_buf = None
         self._record_alt = None
         self._nav_ws = None
+        self._dwa_tables = self._dwa_cost = None
         self.bev = None
         had_ring = self.ring == "seamless"
         self._ring = None  # the seamless ring's pieces return to the process pool ...

@@ -50,6 +50,9 @@
  *   ffmp_frame_potential -> the potential plane and its gradient (obs.potential, obs.grad) from any of
  *                          those frames instead of from the simulator's discs, and the clearance
  *                          plane underneath [unpinned]
+ *   ffmp_dwa            -> a dynamic-window / trajectory-rollout planner over that cost-to-go plane and
+ *                          that flow: the reference's 28 commands (config.py:28-55) rolled forward,
+ *                          rejected where they meet an obstacle at the time the robot is there [unpinned]
  *   ffmp_reward_done    -> FFMP.rewarder / rewarder2 / reward_calculator /
  *                          is_goal / is_done (src/gym_ffmp/envs/ffmp.py:120-188)
  *   ffmp_footprint_collision -> FFMP.is_collision (ffmp.py:85-105)
@@ -907,6 +910,71 @@ int ffmp_frame_potential(const ffmp_cfg_t* cfg, int64_t n, const void* frame, in
                          int32_t potential_format, float* grad, int32_t* robot_d2, void* stream);
 int ffmp_frame_potential_check(const ffmp_cfg_t* cfg, int32_t frame_format, int32_t potential_format, int32_t occ_min,
                                int32_t reach);
+
+/* The rollout (dynamic-window) planner (an addition within ABI 9: no existing symbol, struct or value changes):
+ * A candidate commands (v, w), each rolled forward on the host through the robot's own unicycle into a table of
+ * cell offsets, are tested step by step against the cost-to-go plane of ffmp_nav_field and against the cells the
+ * moving obstacles cover AT THAT STEP — a cost per cell and time instead of ffmp_flow_predict's one gated plane —
+ * and the admissible candidate that ends lowest on the field is chosen.  With the reference's 4 speeds x 7 turn
+ * rates (robot/config.py:28-55) as the candidates, m = 7*vi + wi, the choice is also a valid action id.  No
+ * reference counterpart [unpinned]; the SPEC below is the definition.
+ * SPEC, per env.  c = G/2.  cost: an ffmp_nav_field cost plane, G x G uint16, 65535 = hard or unreachable.  F, vx,
+ * vy: a frame and its flow planes exactly as ffmp_flow_predict takes them (binary16 converted to float32 first), or
+ * both NULL: no moving sources.  Knobs: cps (float32, cells per m/s per rollout step: a caller passes
+ * (float)(stride * dt / res)); src_reach R 0..G; A 1..64 candidates; H 1..32 steps.
+ * traj: int16 (A, H + 1, 2), traj[m][k-1] the cell offset of candidate m from the robot cell after k steps,
+ * traj[m][H] its probe (the endpoint pushed forward along the final heading); cmds: float64 (A, 2), the command
+ * (v_m, w_m) of candidate m.  All trigonometry is the caller's; integers only from here on.
+ * Moving sources (ffmp_flow_predict's rules):
+ *   src[a]  = F[a] == 255, looked at only where |i - c| <= R and |j - c| <= R
+ *   su = vx[a] * cps;  sv = vy[a] * cps     (one float32 multiply each, no contraction)
+ *   a source is skipped if su or sv is not finite, or both are 0
+ *   for k = 1..H:  t = a + ((int)rintf((float)k * su), (int)rintf((float)k * sv))     (half to even)
+ *       skipped if t lies outside 0..G-1 or a rounded displacement is G cells or more (an overflow to
+ *       infinity included: no integer is formed for it);  hit_k = the set of those t
+ * Per candidate m:
+ *   win(m)  = vel == NULL, or  fabs(v_m - vel[e][0]) <= dv_max && fabs(w_m - vel[e][1]) <= dw_max   (float64; a NaN fails)
+ *   p_k     = c + traj[m][k-1]
+ *   blocked at k:  p_k outside 0..G-1,  or  cost[p_k] == 65535,  or  p_k + f in hit_k for a footprint offset f of cfg
+ *   kb(m)   = the first such k, H + 1 if there is none
+ *   blocked_at[e][m] = win ? kb : 0          (uint8)
+ *   admissible  iff  win && kb == H + 1
+ * Score (uint32):  g = cost[p_H];  h = cost[c + traj[m][H]] if the probe lies in the grid on a cost below 65535,
+ *   else 65534;  J = g + h.
+ * Choice: the admissible m with the least J; the lowest m wins ties.
+ * Outputs, each written only when non-NULL: choice int32 (n), -1 when no candidate is admissible; cmd float64
+ * (n, 2), 16-byte aligned: cmds[choice], or (0, 0); score uint32 (n): J, or 0xFFFFFFFF; n_adm int32 (n), the
+ * number of admissible candidates; blocked_at uint8 (n, A).
+ * Mask: an env with mask[e] == 0 keeps every output word.
+ * Parity: integer arithmetic apart from the two multiplies, (float)k * s and the float64 window test; the hits are
+ * ORed and a minimum is taken, so no order shows: the kernel equals tests/dwa_ref.py bit for bit.
+ * Limits.  |traj offset| <= 28 is the caller's contract (the table is device memory; config.rollout_table enforces
+ * it): with |footprint offset| <= 3 everything a rollout can ask about lies within 31 cells of the robot — one
+ * 64 x 64 window per step, one 64-bit word per window row.  An entry beyond 28 is still tested against the grid
+ * and the cost plane, but not against the moving sources.  Known limits: present occupancy stays hard at every k
+ * (the cost plane holds it: cells a disc is leaving are not freed); the prediction is constant-velocity; nothing
+ * is checked between successive k (a thin obstacle faster than a cell per step can be stepped over); the
+ * candidate set is discrete.
+ * cfg: grid and the footprint offsets are read.  cost: DEVICE uint16 (n, G, G), env e at e * cost_env_stride
+ * elements.  frame, frame_env_stride, frame_format, flow, flow_env_stride, flow_format: as for ffmp_flow_predict.
+ * traj, cmds: DEVICE, shared by the envs.  vel: DEVICE float64 (n, 2), the robot's present (v, w), or NULL.
+ * mask: (n) bytes or NULL.
+ * FFMP_E_ARG, with a message and before any HIP call, for: a grid outside 8..512 or not a multiple of 4; an unknown
+ * format; cps not finite or < 0; src_reach outside 0..G; A outside 1..64; H outside 1..32; dv_max or dw_max < 0 or
+ * NaN; a footprint offset above 3 (max |footprint offset| + 28 > 31); cost, traj or cmds NULL; one of frame and
+ * flow NULL without the other; every output NULL; a stride that is too small (cost and frame G*G, flow 2*G*G) or
+ * so large that the n envs do not fit 64 bits of address;
+ * misaligned planes or strides (cost 2 bytes; frame and flow 4 bytes with strides multiples of 4 elements; traj 4,
+ * cmds and vel 8, choice, score and n_adm 4, cmd 16 bytes); an output that overlaps an input; n < 0 or too large
+ * for one launch.  n == 0: nothing is launched.
+ * ffmp_dwa_check: the checks that need no pointer (shape, formats, knobs, footprint), no launch. */
+int ffmp_dwa(const ffmp_cfg_t* cfg, int64_t n, const uint16_t* cost, int64_t cost_env_stride, const void* frame,
+             int64_t frame_env_stride, int32_t frame_format, const void* flow, int64_t flow_env_stride, int32_t flow_format,
+             float cps, int32_t src_reach, const int16_t* traj, const double* cmds, int32_t A, int32_t H, const double* vel,
+             double dv_max, double dw_max, const uint8_t* mask, int32_t* choice, double* cmd, uint32_t* score, int32_t* n_adm,
+             uint8_t* blocked_at, void* stream);
+int ffmp_dwa_check(const ffmp_cfg_t* cfg, int32_t frame_format, int32_t flow_format, float cps, int32_t src_reach, int32_t A,
+                   int32_t H, double dv_max, double dw_max);
 
 /* Standalone reward/done (FFMP.rewarder / rewarder2 semantics), n envs:
  *   scan:   (n, scan_len) float64 ranges (0 = skipped, as `if scan_data[i]`), or NULL
