@@ -158,6 +158,13 @@ _SIGS = {
                                 _I64, _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P]),
     "ffmp_scan_map_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32,
                                       _I32, _I32, _I32]),
+    # the world-fixed scan map and its ego view (an addition within ABI 9): log-odds per world cell, updated in place
+    "ffmp_world_map": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _I64, _P, _P, _P, _I64, _I32, C.c_float,
+                                 C.c_float, _I32, _I32, _I32, _I32, _I32, _P]),
+    "ffmp_world_map_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, C.c_float, C.c_float, _I32, _I32, _I32, _I32, _I32]),
+    "ffmp_world_frame": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _I32,
+                                   _P]),
+    "ffmp_world_frame_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, _I32, _I32]),
     # motion flow estimated from two scan frames (an addition within ABI 9): block matching, ego-motion compensated
     "ffmp_scan_flow": (C.c_int, [C.POINTER(CfgT), _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32,
                                  C.c_float, _I32, _I32, _I32, _I32, _P]),

@@ -409,6 +409,14 @@ class FFMP(GymEnvBase):
             raise RuntimeError("call reset() before lidar_map()")
         return self._vec_env().lidar_map(**kw)
 
+    def world_map(self, **kw):
+        """The world-fixed scan map of this one env (FFMPVec.world_map, include/ffmp.h ffmp_world_map /
+        ffmp_world_frame): the WorldMap holder of the inner batched env — update() it after reset() /
+        step(); its `log_odds` (1, cells, cells) and ego_frame() (1, G, G) are device tensors."""
+        if self._vec is None:
+            raise RuntimeError("call reset() before world_map()")
+        return self._vec_env().world_map(**kw)
+
     def lidar_flow(self, **kw):
         """The motion flow estimated from this one env's scan (FFMPVec.lidar_flow, include/ffmp.h
         ffmp_scan_flow): the LidarFlow holder of the inner batched env — update() it after reset() /

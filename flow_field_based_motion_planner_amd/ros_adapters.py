@@ -27,7 +27,8 @@ conversions keep the reference's exact semantics:
                                      twist_to_command: the way back, a /cmd_vel Twist -> (v, w)
                                      for FFMPVec.step / FFMP.step
 
-and the other direction, env -> messages: lidar_to_ranges, frame_to_image, pose_to_odometry.
+and the other direction, env -> messages: lidar_to_ranges, frame_to_image, pose_to_odometry, and
+world_map_to_occupancy_grid (one env's WorldMap plane as a dict shaped like nav_msgs/OccupancyGrid).
 Host-side (numpy): a bridge talks to one robot at a time.
 """
 from __future__ import annotations
@@ -269,3 +270,27 @@ def pose_to_odometry(x: float, y: float, yaw: float, stamp: float) -> Msg:
     return Msg(header={"stamp": {"secs": secs, "nsecs": int(round((stamp - secs) * 1e9))}},
                pose={"pose": {"position": {"x": x, "y": y, "z": 0.0},
                               "orientation": {"x": qx, "y": qy, "z": qz, "w": qw}}})
+
+
+def world_map_to_occupancy_grid(log_odds_row: np.ndarray, resolution: float, origin, occ_thr: int = 8, free_thr: int = 4) -> dict:
+    """One env's plane of a WorldMap (`log_odds[e]`, (cells, cells) int8, row p world x, column q world
+    y) as a plain dict shaped like nav_msgs/OccupancyGrid.  `data` is int8, -1 unknown, 0 free (log-odds
+    <= -free_thr), 100 occupied (>= occ_thr), in the row-major order ROS expects, x fastest:
+    data[y * width + x] is cell (x, y) — the plane TRANSPOSED and then flattened, since the plane's
+    rows are x.  `origin`: WorldMap.origin, the world coordinate of the CENTRE of cell (0, 0) (a scalar
+    for both axes, or (x, y)); info.origin.position is the lower-left CORNER of that cell, as ROS defines
+    it, half a cell less.  The map's axes are the world's: the orientation is the identity."""
+    m = np.asarray(log_odds_row)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("log_odds_row must be (cells, cells)")
+    if not 1 <= int(occ_thr) <= 127 or not 1 <= int(free_thr) <= 127:
+        raise ValueError("occ_thr and free_thr must be in [1, 127]")
+    ox, oy = (origin, origin) if np.ndim(origin) == 0 else origin
+    m = m.astype(np.int32)
+    val = np.where(m >= int(occ_thr), 100, np.where(m <= -int(free_thr), 0, -1)).astype(np.int8)
+    res = float(resolution)
+    return {"header": {"frame_id": "map"},
+            "info": {"resolution": res, "width": int(m.shape[0]), "height": int(m.shape[1]),
+                     "origin": {"position": {"x": float(ox) - 0.5 * res, "y": float(oy) - 0.5 * res, "z": 0.0},
+                                "orientation": {"x": 0.0, "y": 0.0, "z": 0.0, "w": 1.0}}},
+            "data": np.ascontiguousarray(val.T).reshape(-1)}

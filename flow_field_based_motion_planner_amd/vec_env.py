@@ -31,6 +31,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import weakref
 from typing import Dict, Optional, Tuple, Union
 
 import numpy as np
@@ -1989,6 +1990,37 @@ class FFMPVec:
                         self.cfg.lidar_range if range_max is None else range_max, l_hit, l_free, l_max, decay, occ_thr,
                         free_thr, frame)
 
+    # ------------------------------------------------ the world-fixed scan map
+    def world_map(self, cells: Optional[int] = None, unknown: int = 128, outside: int = 255, thickness: Optional[float] = None,
+                  range_max: Optional[float] = None, l_hit: int = 8, l_free: int = 4, l_max: int = 64, decay: int = 0,
+                  occ_thr: int = 8, free_thr: int = 4) -> "WorldMap":
+        """The /map of occupancy-grid mapping (include/ffmp.h ffmp_world_map / ffmp_world_frame): an int8
+        log-odds plane per env with one cell per WORLD cell, `cells` x `cells` of them centred on the world's
+        origin, integrated in place from the scan and the pose by every WorldMap.update() and never re-sampled
+        — edges do not jitter, and what leaves the ego window is remembered.  WorldMap.ego_frame() cuts the
+        window around the robot out and rotates it into the ego frame: 255 where the log-odds are >=
+        `occ_thr`, 0 where <= -`free_thr`, `unknown` elsewhere and `outside` beyond the plane — a plane for
+        nav_field / policy_nav / policy_dwa / frame_potential through frames=.  cells: a multiple of 4 in
+        [8, 2048]; by default the arena [-world_half, world_half] plus four cells a side.  thickness,
+        range_max, l_hit, l_free, l_max, decay: as for lidar_map, but a cell the scan does not reach
+        (beyond range_max, or in a cone without data) keeps its value with no decay.  Memory: cells^2
+        bytes per env.  Known limit: a moving obstacle leaves a trail of stale hits until the beam
+        sweeps it free again."""
+        self._check_open()
+        if cells is None:
+            cells = 4 * int(math.ceil((2.0 * self.cfg.W / self.cfg.res + 8.0) / 4.0))
+        cells = int(cells)
+        if cells > 2048:
+            raise ValueError(f"world_map: cells = {cells} is above 2048 ({self.num_envs} envs x {cells}^2 bytes = "
+                             f"{self.num_envs * cells * cells / 1e9:.2f} GB of log-odds); use a coarser res or a smaller world_half")
+        holder = WorldMap(self, cells, unknown, outside, self.cfg.res if thickness is None else thickness,
+                          self.cfg.lidar_range if range_max is None else range_max, l_hit, l_free, l_max, decay, occ_thr,
+                          free_thr)
+        if self._world_maps is None:
+            self._world_maps = []
+        self._world_maps.append(weakref.ref(holder))
+        return holder
+
     # ------------------------------------------------ motion flow estimated from the scan (DESIGN §3 a19d, §5.13)
     def lidar_flow(self, lag: int = 4, radius: int = 4, block: int = 3, gate: int = 1, min_hits: int = 3,
                    thickness: Optional[float] = None, range_max: Optional[float] = None, kind: bool = True) -> "LidarFlow":
@@ -2563,6 +2595,11 @@ class FFMPVec:
         self._record_alt = None
         self._nav_ws = None
         self._dwa_tables = self._dwa_cost = None
+        for ref in self._world_maps or ():
+            holder = ref()
+            if holder is not None:
+                holder._release()
+        self._world_maps = None
         self.bev = None
         had_ring = self.ring == "seamless"
         self._ring = None  # the seamless ring's pieces return to the process pool ...
@@ -2574,6 +2611,7 @@ class FFMPVec:
             _abi.ring_pool_trim(self.device.index, self.pool_keep_bytes)  # ... and their memory to the device
 
     _closed = False
+    _world_maps = None  # weak references to the WorldMap holders of world_map(): close() releases their planes
     bev = None  # the BEV image ring (bev_series); a class default: _alloc's HBM accounting runs first
 
     def _check_open(self) -> None:
@@ -2766,6 +2804,155 @@ class LidarMap:
             self._episode.copy_(torch.where(sel, episode, self._episode))
         self._cur = 1 - self._cur
         return self.frame
+
+
+class WorldMap:
+    """The world-fixed scan map of an FFMPVec (FFMPVec.world_map; include/ffmp.h ffmp_world_map /
+    ffmp_world_frame): one (N, cells, cells) int8 log-odds plane, row p world x and
+    column q world y, cell (p, q) centred on (origin + p * resolution, origin + q * resolution), updated
+    in place — no second plane — and the episode ids of the last update, so a missed auto-reset still
+    restarts the env.  The step, its frames, its lidar and its record are never written; the env's
+    close() releases the plane."""
+
+    def __init__(self, env: FFMPVec, cells: int, unknown: int, outside: int, thickness: float, range_max: float, l_hit: int,
+                 l_free: int, l_max: int, decay: int, occ_thr: int, free_thr: int):
+        self.env = env
+        self.cells = int(cells)
+        self.knobs = (float(thickness), float(range_max), int(l_hit), int(l_free), int(l_max), int(decay))
+        self.view = (env._fmt, int(unknown), int(outside), int(occ_thr), int(free_thr))
+        _abi.check(env.lib.ffmp_world_map_check(C.byref(env._cfg_c), 1, self.cells, *self.knobs, 0), "ffmp_world_map_check")
+        _abi.check(env.lib.ffmp_world_frame_check(C.byref(env._cfg_c), self.cells, *self.view), "ffmp_world_frame_check")
+        n = env.num_envs
+        self._plane = torch.zeros((n, self.cells, self.cells), dtype=torch.int8, device=env.device)
+        self._episode = torch.full((n,), -1, dtype=torch.int32, device=env.device)  # no episode: every env restarts
+
+    @property
+    def log_odds(self) -> torch.Tensor:
+        """The (N, cells, cells) int8 plane: 0 nothing known, positive occupied, negative free."""
+        self._check()
+        return self._plane
+
+    @property
+    def resolution(self) -> float:
+        """Metres per cell: the env's res."""
+        return float(self.env.cfg.res)
+
+    @property
+    def origin(self) -> float:
+        """World coordinate (both axes) of the centre of cell (0, 0): -(float32)(cells * res / 2)."""
+        return -float(np.float32(self.cells * self.env.cfg.res / 2.0))
+
+    @property
+    def bytes(self) -> int:
+        """Device bytes of the log-odds plane."""
+        return self.env.num_envs * self.cells * self.cells
+
+    def _check(self) -> None:
+        if self._plane is None:
+            raise RuntimeError("the WorldMap's env is closed")
+
+    def _release(self) -> None:
+        self._plane = self._episode = None
+
+    def _mask(self, mask) -> Optional[torch.Tensor]:
+        if mask is None:
+            return None
+        return torch.as_tensor(mask, device=self.env.device).reshape(self.env.num_envs).to(torch.uint8).contiguous()
+
+    def _pose(self, pose) -> torch.Tensor:
+        env = self.env
+        if pose is None:
+            return env.record
+        n = env.num_envs
+        if not isinstance(pose, torch.Tensor) or tuple(pose.shape) != (n, 4) or pose.dtype != torch.float32 \
+                or not pose.is_contiguous() or pose.device != env.device:
+            raise ValueError(f"pose must be a contiguous float32 tensor of shape ({n}, 4) on {env.device}")
+        return pose
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Forget the map of the selected envs (mask: (N,) bool or uint8; None = all): log-odds 0, and the
+        next update restarts them."""
+        self._check()
+        if mask is None:
+            self._plane.zero_()
+            self._episode.fill_(-1)
+            return
+        sel = self._mask(mask).bool()
+        self._plane[sel] = 0
+        self._episode[sel] = -1
+
+    def update(self, ranges: Optional[torch.Tensor] = None, pose: Optional[torch.Tensor] = None,
+               first: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, plain: bool = False) -> torch.Tensor:
+        """Add the current scan at the current pose: one launch on the current stream, in place, then one
+        tiny copy (the episode ids) on the same stream.  Returns the log-odds plane.
+        ranges, pose, first, mask, plain: LidarMap.update's conventions — ranges a contiguous (N, L')
+        float32 device tensor instead of the env's `lidar`; pose a contiguous (N, 4) float32 device tensor
+        {x, y, cos yaw, sin yaw} instead of record words 0..3, and then the env's own bookkeeping is not
+        looked at: without first= no env restarts (but those never updated or reset()); first: (N,)
+        bool, the envs whose map starts anew, by default those whose episode id has changed since the
+        last update or whose record says it has just reset; mask: envs with 0 keep their map."""
+        env = self.env
+        env._check_open()
+        self._check()
+        if env._needs_reset:
+            raise RuntimeError("call reset() before WorldMap.update()")
+        n = env.num_envs
+        if ranges is None:
+            if env.lidar is None:
+                raise ValueError("WorldMap.update: the env has n_beams == 0, pass ranges=")
+            ranges = env.lidar
+        elif not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 or ranges.shape[0] != n or ranges.dtype != torch.float32 \
+                or not ranges.is_contiguous() or ranges.device != env.device:
+            raise ValueError(f"ranges must be a contiguous float32 tensor of shape ({n}, L) on {env.device}")
+        never = self._episode < 0
+        if pose is None:
+            if first is None:
+                first = (env.episode != self._episode) | (env.record[:, 10] != 0)
+            episode = env.episode
+        else:
+            episode = torch.zeros_like(self._episode)
+        pose = self._pose(pose)
+        if first is None:
+            first = never
+        else:
+            first = torch.as_tensor(first, device=env.device).reshape(n).bool() | never
+        mask = self._mask(mask)
+        L = int(ranges.shape[1])
+        flags = _abi.SCAN_PLAIN if plain else 0
+        _abi.check(env.lib.ffmp_world_map_check(C.byref(env._cfg_c), L, self.cells, *self.knobs, flags), "ffmp_world_map_check")
+        sectors = env._sectors(L)
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_world_map(C.byref(env._cfg_c), n, ranges.data_ptr(), ranges.stride(0), L, sectors.data_ptr(),
+                                              pose.data_ptr(), pose.stride(0), _ptr(mask), first.data_ptr(),
+                                              self._plane.data_ptr(), self.cells * self.cells, self.cells, *self.knobs, flags,
+                                              env._stream()), "ffmp_world_map")
+        if mask is None:
+            self._episode.copy_(episode)
+        else:
+            self._episode.copy_(torch.where(mask.bool(), episode, self._episode))
+        return self._plane
+
+    def ego_frame(self, pose: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The map as the robot at `pose` (by default the env's current pose) sees it: (N, G, G) in the
+        env's frame dtype — one launch on the current stream, read-only on the map.  out: a contiguous
+        tensor of that shape and dtype to write into."""
+        env = self.env
+        env._check_open()
+        self._check()
+        if pose is None and env._needs_reset:
+            raise RuntimeError("call reset() before WorldMap.ego_frame()")
+        pose = self._pose(pose)
+        n, G = env.num_envs, env.cfg.grid
+        if out is None:
+            out = torch.empty((n, G, G), dtype=env._frame_dtype, device=env.device)
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, G, G) or out.dtype != env._frame_dtype \
+                or not out.is_contiguous() or out.device != env.device:
+            raise ValueError(f"out must be a contiguous {env._frame_dtype} tensor of shape ({n}, {G}, {G}) on {env.device}")
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_world_frame(C.byref(env._cfg_c), n, pose.data_ptr(), pose.stride(0), self._plane.data_ptr(),
+                                                self.cells * self.cells, self.cells, out.data_ptr(), G * G, *self.view,
+                                                env._stream()), "ffmp_world_frame")
+        return out
 
 
 class LidarFlow:

@@ -42,6 +42,8 @@
  *                          inverse sensor model, this header's own [unpinned]
  *   ffmp_scan_map       -> that image with a memory: int8 log-odds per cell, moved with the
  *                          robot's own motion and updated from every scan [unpinned]
+ *   ffmp_world_map / ffmp_world_frame -> the /map a ROS graph keeps beside /scan and /odom: int8
+ *                          log-odds per WORLD cell, never re-sampled, and its ego view [unpinned]
  *   ffmp_scan_flow      -> the flow half of that image (the RGB of "occupancy(MONO) + flow(RGB)",
  *                          src/gym_ffmp/envs/ffmp.py:16) from two scan frames and the two poses: a
  *                          per-cell velocity by block matching with ego-motion compensation [unpinned]
@@ -741,6 +743,72 @@ int ffmp_scan_map(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t
 int ffmp_scan_map_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t format, int32_t unknown, float thickness,
                         float range_max, int32_t l_hit, int32_t l_free, int32_t l_max, int32_t decay, int32_t occ_thr,
                         int32_t free_thr, int32_t flags);
+
+/* The world-fixed scan map (an addition within ABI 9: no existing symbol, struct or value changes) —
+ * ffmp_scan_map re-samples its plane into the new ego frame on every update (edges jitter, and what
+ * leaves the G x G window is forgotten); this map has one log-odds cell per WORLD cell, is updated in
+ * place and never re-sampled, and is cut out and rotated into the ego frame only when asked
+ * (ffmp_world_frame).  No reference counterpart [unpinned]; the SPEC below is the definition.
+ * State: one int8 plane per env, M (Wc x Wc), Wc = `cells` a multiple of 4 in [8, 2048]: cell (p, q) of
+ * env e at e * map_env_stride + p*Wc + q bytes; the pointer 4-byte aligned, map_env_stride a multiple of 4
+ * and >= Wc*Wc.  Row p is world x, column q is world y.  World cell centres, float32:
+ *   wh_f = (float)(Wc * res / 2)                       (cfg.res, float64 on the host, then rounded)
+ *   wx = (float)p * res_f - wh_f;  wy = (float)q * res_f - wh_f
+ * so the plane is centred on the world's origin and covers [-wh_f, wh_f).
+ *
+ * ffmp_world_map: the update, in place, one launch.  ranges, ranges_stride, n_beams, sectors, thickness,
+ * range_max, the knobs l_hit, l_free, l_max, decay (their ranges included) and FFMP_SCAN_PLAIN (no search
+ * shortcut, the same bits) are as in ffmp_scan_map.  pose: DEVICE memory, env e's four float32 words
+ * {px, py, c, s} (record words 0..3: position, cos yaw, sin yaw) at pose + e * pose_stride floats,
+ * pose_stride >= 4.  Per world cell (p, q): float32, no FMA contraction, operation order as written.
+ *   dx = wx - px;  dy = wy - py
+ *   ex = c*dx + s*dy;  ey = c*dy - s*dx
+ * The class of the cell is ffmp_scan_frames' classification verbatim with these (ex, ey) in place of the
+ * grid's cell coordinates: the half-turn from c0, the bisection over the sector table, r, b, known, free,
+ * occ.  Update, int32 arithmetic, stored as int8:
+ *   not known (b > range_max^2, or no data in its cone):  M unchanged
+ *   free:                 M = clamp(M - l_free, -l_max, l_max)
+ *   occ and not free:     M = clamp(M + l_hit, -l_max, l_max)
+ *   known, neither:       M = M - sgn(M) * min(|M|, decay)
+ * Not-known cells keep their value, so an implementation may visit any superset of the sensor disc's
+ * bounding box (the kernel: that box clipped to the plane, columns rounded out to multiples of 4; the
+ * whole plane for a range_max whose float32 square is +inf) and gives the same bits.
+ * Per env: mask[e] == 0 (mask: (n) bytes or NULL = all) leaves every byte of the env unchanged.
+ * first[e] != 0 (first: (n) bytes or NULL = none) zeroes the env's whole plane before the update.  A
+ * non-finite pose word leaves the plane as it is — as it is after the zeroing, for an env with first set.
+ * FFMP_E_ARG, with a message and before any HIP call, for: cfg NULL or res_f not > 0; cells outside
+ * 8..2048 or not a multiple of 4; n_beams outside 1..FFMP_MAX_BEAMS; thickness NaN, negative or infinite;
+ * range_max NaN or <= 0; a knob out of range; unknown flag bits; ranges, sectors, pose or map NULL;
+ * ranges_stride < n_beams; pose_stride < 4; map_env_stride < Wc*Wc; a misaligned map or stride; n < 0 or
+ * too large for one launch.  n == 0: nothing is launched.
+ * ffmp_world_map_check: the checks that need no pointer (shape, knobs), no launch.
+ *
+ * ffmp_world_frame: the ego view, one launch, read-only on the map.  Per ego cell (i, j), float32 as above:
+ *   ex = (float)i * res_f - half_f;  ey = (float)j * res_f - half_f      (the raster's cell coordinates)
+ *   wx = (c*ex - s*ey) + px;  wy = (s*ex + c*ey) + py
+ *   fp = rintf((wx + wh_f) / res_f);  fq = rintf((wy + wh_f) / res_f)     (rounding half to even)
+ *   inside = fp >= 0 && fp <= Wc - 1 && fq >= 0 && fq <= Wc - 1           (float compares: a NaN is outside)
+ *   value = !inside ? outside : M[fp][fq] >= occ_thr ? 255 : M[fp][fq] <= -free_thr ? 0 : unknown
+ * outside, unknown: bytes 0..255; 1 <= occ_thr, free_thr <= 127.  An env with a non-finite pose word gets
+ * a frame of `unknown` only.  frame_out: FFMP_OBS_F32 writes (float)value, FFMP_OBS_U8F16 the byte;
+ * addressed and aligned as ffmp_scan_frames' outputs with frame_env_stride (16- or 4-byte aligned, the
+ * stride a multiple of 4 elements and >= G*G).
+ * FFMP_E_ARG, with a message and before any HIP call, for: cfg NULL or res_f not > 0; cells or grid out of
+ * range; an unknown format; unknown or outside outside 0..255; a threshold out of range; pose, map or
+ * frame_out NULL; a stride that is too small; a misaligned frame or stride; a frame whose bytes overlap
+ * the map's; n < 0 or too large for one launch.  n == 0: nothing is launched.
+ * ffmp_world_frame_check: the checks that need no pointer (shape, format, knobs), no launch. */
+int ffmp_world_map(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t ranges_stride, int32_t n_beams,
+                   const float* sectors, const float* pose, int64_t pose_stride, const uint8_t* mask, const uint8_t* first,
+                   int8_t* map, int64_t map_env_stride, int32_t cells, float thickness, float range_max, int32_t l_hit,
+                   int32_t l_free, int32_t l_max, int32_t decay, int32_t flags, void* stream);
+int ffmp_world_map_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t cells, float thickness, float range_max,
+                         int32_t l_hit, int32_t l_free, int32_t l_max, int32_t decay, int32_t flags);
+int ffmp_world_frame(const ffmp_cfg_t* cfg, int64_t n, const float* pose, int64_t pose_stride, const int8_t* map,
+                     int64_t map_env_stride, int32_t cells, void* frame_out, int64_t frame_env_stride, int32_t format,
+                     int32_t unknown, int32_t outside, int32_t occ_thr, int32_t free_thr, void* stream);
+int ffmp_world_frame_check(const ffmp_cfg_t* cfg, int32_t cells, int32_t format, int32_t unknown, int32_t outside,
+                           int32_t occ_thr, int32_t free_thr);
 
 /* Motion flow estimated from the scan (an addition within ABI 9: no existing symbol, struct or value
  * changes): the sensor-side counterpart of the flow planes of cfg.flow.  Two scan frames `lag` updates
