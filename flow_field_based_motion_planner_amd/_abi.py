@@ -165,6 +165,10 @@ _SIGS = {
     "ffmp_world_frame": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _P, _I64, _I32, _P, _I64, _I32, _I32, _I32, _I32, _I32,
                                    _P]),
     "ffmp_world_frame_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, _I32, _I32]),
+    # scan-to-map matching (an addition within ABI 9): the pose corrected against the world map, a correlative search
+    "ffmp_scan_match": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _I32, _I32,
+                                  C.c_float, _I32, _I32, _P, _P, _P, _I32, _P]),
+    "ffmp_scan_match_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, C.c_float, _I32, _I32, _I32]),
     # motion flow estimated from two scan frames (an addition within ABI 9): block matching, ego-motion compensated
     "ffmp_scan_flow": (C.c_int, [C.POINTER(CfgT), _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32,
                                  C.c_float, _I32, _I32, _I32, _I32, _P]),
@@ -294,6 +298,7 @@ RASTER_WAVES = 1024  # float32 frames with granule tags: the kernel held to 6 wa
 RASTER_DIRECT = 2048  # beside RASTER_WAVES, two-launch raster: blocks without LDS or barrier, one memory round trip
 VISIBLE_NOCULL = 1  # FFMP_VISIBLE_NOCULL: ffmp_visible_frames without its culls (the same bits)
 SCAN_PLAIN = 1  # FFMP_SCAN_PLAIN: ffmp_scan_frames with the SPEC's bisection for every cell (the same bits)
+MATCH_GLOBAL = 1  # FFMP_MATCH_GLOBAL: ffmp_scan_match gathering from global memory — what it always does; accepted, no effect
 
 
 def set_tuning(key: int, value: int) -> int:

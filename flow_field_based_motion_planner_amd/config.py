@@ -134,6 +134,25 @@ def beam_table(n_beams: int) -> np.ndarray:
     return out
 
 
+def beam_dirs(n_beams: int) -> np.ndarray:
+    """(L, 2) float32: beam_table rounded — the `beams` table of ffmp_scan_match (include/ffmp.h)."""
+    return beam_table(n_beams).astype(np.float32)
+
+
+def turn_table(turns: int, dtheta: float) -> np.ndarray:
+    """(2T + 1, 2) float32 {cos, sin} of (k - T) * dtheta, math.cos / math.sin of the float64 angle rounded:
+    the rotation steps of ffmp_scan_match (include/ffmp.h).  Entry T is exactly (1, 0)."""
+    turns = int(turns)
+    if turns < 0:
+        raise ValueError(f"turns must be >= 0, got {turns}")
+    out = np.zeros((2 * turns + 1, 2), dtype=np.float32)
+    for k in range(2 * turns + 1):
+        th = (k - turns) * float(dtheta)
+        out[k, 0] = math.cos(th)
+        out[k, 1] = math.sin(th)
+    return out
+
+
 def sector_table(n_beams: int) -> np.ndarray:
     """(L, 2) float32 {cos, sin} of the cone boundaries -pi + (m - 1/2)*2pi/L (robot frame), each the
     float32 rounding of math.cos / math.sin of the float64 angle: sector m, from boundary m to

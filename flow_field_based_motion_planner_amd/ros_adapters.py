@@ -27,8 +27,10 @@ conversions keep the reference's exact semantics:
                                      twist_to_command: the way back, a /cmd_vel Twist -> (v, w)
                                      for FFMPVec.step / FFMP.step
 
-and the other direction, env -> messages: lidar_to_ranges, frame_to_image, pose_to_odometry, and
-world_map_to_occupancy_grid (one env's WorldMap plane as a dict shaped like nav_msgs/OccupancyGrid).
+and the other direction, env -> messages: lidar_to_ranges, frame_to_image, pose_to_odometry,
+world_map_to_occupancy_grid (one env's WorldMap plane as a dict shaped like nav_msgs/OccupancyGrid) and
+map_to_odom_transform (the map -> odom transform a localisation node publishes, from the pose
+WorldMap.match found, as a dict shaped like geometry_msgs/TransformStamped).
 Host-side (numpy): a bridge talks to one robot at a time.
 """
 from __future__ import annotations
@@ -294,3 +296,24 @@ def world_map_to_occupancy_grid(log_odds_row: np.ndarray, resolution: float, ori
                      "origin": {"position": {"x": float(ox) - 0.5 * res, "y": float(oy) - 0.5 * res, "z": 0.0},
                                 "orientation": {"x": 0.0, "y": 0.0, "z": 0.0, "w": 1.0}}},
             "data": np.ascontiguousarray(val.T).reshape(-1)}
+
+
+def map_to_odom_transform(odom_row, matched_row, stamp: float) -> dict:
+    """The `map -> odom` transform of a localisation node as a plain dict shaped like
+    geometry_msgs/TransformStamped: the rigid motion that takes the odometry pose `odom_row` to the pose
+    `matched_row` that WorldMap.match / the localizer found for the same instant — both rows of four words
+    {x, y, cos yaw, sin yaw} (odom_to_pose_row's layout).  yaw = yaw(matched) - yaw(odom), wrapped into
+    (-pi, pi]; translation = matched position - R(yaw) odom position; the rotation is yaw_to_quaternion's.
+    Composed with the odometry pose it gives the matched pose back; equal rows give the identity."""
+    o = np.asarray(odom_row, dtype=np.float64).reshape(-1)
+    m = np.asarray(matched_row, dtype=np.float64).reshape(-1)
+    if o.shape[0] < 4 or m.shape[0] < 4:
+        raise ValueError("odom_row and matched_row must hold the four words {x, y, cos yaw, sin yaw}")
+    yaw = _wrap_pi(math.atan2(m[3], m[2]) - math.atan2(o[3], o[2]))
+    c, s = math.cos(yaw), math.sin(yaw)
+    qx, qy, qz, qw = yaw_to_quaternion(yaw)
+    secs = int(math.floor(stamp))
+    return {"header": {"stamp": {"secs": secs, "nsecs": int(round((stamp - secs) * 1e9))}, "frame_id": "map"},
+            "child_frame_id": "odom",
+            "transform": {"translation": {"x": float(m[0] - (c * o[0] - s * o[1])), "y": float(m[1] - (s * o[0] + c * o[1])), "z": 0.0},
+                          "rotation": {"x": qx, "y": qy, "z": qz, "w": qw}}}

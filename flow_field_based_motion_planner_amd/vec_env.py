@@ -38,7 +38,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from .config import PRESETS, FFMPConfig, beam_table, preset, rollout_horizon, rollout_table, sector_table
+from .config import (PRESETS, FFMPConfig, beam_dirs, beam_table, preset, rollout_horizon, rollout_table, sector_table,
+                     turn_table)
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -2953,6 +2954,132 @@ class WorldMap:
                                                 self.cells * self.cells, self.cells, out.data_ptr(), G * G, *self.view,
                                                 env._stream()), "ffmp_world_frame")
         return out
+
+    _match_tables = None  # (L or (T, dtheta)) -> device tensor: config.beam_dirs / config.turn_table
+
+    def _match_table(self, key, make) -> torch.Tensor:
+        if self._match_tables is None:
+            self._match_tables = {}
+        if key not in self._match_tables:
+            self._match_tables[key] = torch.as_tensor(make()).to(self.env.device).contiguous()
+        return self._match_tables[key]
+
+    def match(self, ranges: Optional[torch.Tensor] = None, pose: Optional[torch.Tensor] = None, radius: int = 4, turns: int = 4,
+              dtheta: Optional[float] = None, min_valid: Optional[int] = None, min_gain: int = 0,
+              range_max: Optional[float] = None, detail: bool = False, volume: bool = False, out: Optional[torch.Tensor] = None,
+              mask: Optional[torch.Tensor] = None, flags: int = 0):
+        """The pose corrected against the map (include/ffmp.h ffmp_scan_match): the scan's endpoints scored on
+        the plane at every whole-cell shift within `radius` cells and every rotation of up to `turns` steps of
+        `dtheta` round the prior `pose`, and the best candidate's pose — (N, 4) float32 {x, y, cos yaw, sin yaw},
+        what update(pose=) and ego_frame(pose=) take; an env the gate refuses keeps its prior bit for bit.  One
+        launch on the current stream, read-only on the map.
+        ranges, pose: as update() takes them (by default the env's lidar and record words 0..3).  dtheta: by
+        default res / lidar_range, one cell of arc at full range; min_valid: the fewest valid beams an env is
+        matched on, by default max(8, L // 6); min_gain: the least the best score must exceed the prior's by;
+        range_max: by default the map's.  detail: also return info (N, 8) int32 {status, k, a, b, S_best,
+        S(0,0,0), valid, 0}; volume: also return every score (N, 2 turns + 1, 2 radius + 1, 2 radius + 1) int32.
+        out: a contiguous (N, 4) float32 tensor to write the pose into; mask: envs with 0 keep their row of
+        out (with out=None: their prior).  flags: ffmp_scan_match's (_abi.MATCH_GLOBAL: accepted, no effect)."""
+        env = self.env
+        env._check_open()
+        self._check()
+        if pose is None and env._needs_reset:
+            raise RuntimeError("call reset() before WorldMap.match()")
+        n = env.num_envs
+        if ranges is None:
+            if env.lidar is None:
+                raise ValueError("WorldMap.match: the env has n_beams == 0, pass ranges=")
+            ranges = env.lidar
+        elif not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 or ranges.shape[0] != n or ranges.dtype != torch.float32 \
+                or not ranges.is_contiguous() or ranges.device != env.device:
+            raise ValueError(f"ranges must be a contiguous float32 tensor of shape ({n}, L) on {env.device}")
+        pose = self._pose(pose)
+        L, R, T = int(ranges.shape[1]), int(radius), int(turns)
+        dtheta = env.cfg.res / env.cfg.lidar_range if dtheta is None else float(dtheta)
+        min_valid = max(8, L // 6) if min_valid is None else int(min_valid)
+        rm = self.knobs[1] if range_max is None else float(range_max)
+        _abi.check(env.lib.ffmp_scan_match_check(C.byref(env._cfg_c), L, self.cells, R, T, rm, min_valid, int(min_gain), int(flags)),
+                   "ffmp_scan_match_check")
+        mask = self._mask(mask)
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=env.device)
+            if mask is not None:
+                out.copy_(pose[:, 0:4])
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, 4) or out.dtype != torch.float32 \
+                or not out.is_contiguous() or out.device != env.device:
+            raise ValueError(f"out must be a contiguous float32 tensor of shape ({n}, 4) on {env.device}")
+        info = torch.zeros((n, 8), dtype=torch.int32, device=env.device) if detail else None
+        vol = torch.zeros((n, 2 * T + 1, 2 * R + 1, 2 * R + 1), dtype=torch.int32, device=env.device) if volume else None
+        beams = self._match_table(L, lambda: beam_dirs(L))
+        table = self._match_table((T, dtheta), lambda: turn_table(T, dtheta))
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_scan_match(C.byref(env._cfg_c), n, ranges.data_ptr(), ranges.stride(0), L, beams.data_ptr(),
+                                               pose.data_ptr(), pose.stride(0), _ptr(mask), self._plane.data_ptr(),
+                                               self.cells * self.cells, self.cells, table.data_ptr(), T, R, rm, min_valid,
+                                               int(min_gain), out.data_ptr(), _ptr(info), _ptr(vol), int(flags), env._stream()),
+                       "ffmp_scan_match")
+        if not detail and not volume:
+            return out
+        return (out,) + ((info,) if detail else ()) + ((vol,) if volume else ())
+
+    def localizer(self, radius: int = 2, turns: int = 2, dtheta: Optional[float] = None, min_valid: Optional[int] = None,
+                  min_gain: int = 0, range_max: Optional[float] = None) -> "Localizer":
+        """A holder that keeps the per-env map <- odom transform and corrects every odometry pose against this
+        map before the scan is integrated (Localizer.step)."""
+        self._check()
+        return Localizer(self, radius, turns, dtheta, min_valid, min_gain, range_max)
+
+
+class Localizer:
+    """Scan-to-map localisation over a WorldMap (WorldMap.localizer): `transform` (N, 3)
+    float64 {tx, ty, theta} on the device, the rigid motion that takes an odometry pose into the map's frame.
+    step() composes the prior from it, matches, recomputes it, and updates the map at the matched pose."""
+
+    def __init__(self, world_map: WorldMap, radius: int, turns: int, dtheta, min_valid, min_gain: int, range_max):
+        self.map = world_map
+        self.knobs = dict(radius=int(radius), turns=int(turns), dtheta=dtheta, min_valid=min_valid, min_gain=int(min_gain),
+                          range_max=range_max)
+        env = world_map.env
+        self._tf = torch.zeros((env.num_envs, 3), dtype=torch.float64, device=env.device)
+        self._seen = torch.zeros((env.num_envs,), dtype=torch.bool, device=env.device)
+
+    @property
+    def transform(self) -> torch.Tensor:
+        """(N, 3) float64 {tx, ty, theta}: map <- odom."""
+        return self._tf
+
+    def step(self, odom: torch.Tensor, ranges: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
+             update: bool = True) -> torch.Tensor:
+        """odom: a contiguous (N, 4) float32 device tensor {x, y, cos yaw, sin yaw}, the odometry poses.  The prior
+        is transform o odom (float64, rounded to the four float32 words); the matched pose (N, 4) float32 is
+        returned, `transform` is recomputed from it and the odometry, and with `update` the scan is integrated at
+        it (WorldMap.update(pose=matched, first=...)).  Envs flagged `first` ((N,) bool) and envs never stepped
+        get transform 0 and are not matched on this call: their map is empty."""
+        wm = self.map
+        env = wm.env
+        if odom is None:
+            raise ValueError("Localizer.step: odom is required")
+        odom = wm._pose(odom)
+        n = env.num_envs
+        fresh = ~self._seen
+        if first is not None:
+            fresh = fresh | torch.as_tensor(first, device=env.device).reshape(n).bool()
+        tf = torch.where(fresh.reshape(n, 1), torch.zeros_like(self._tf), self._tf)
+        o = odom.to(torch.float64)
+        ct, st = torch.cos(tf[:, 2]), torch.sin(tf[:, 2])
+        prior = torch.stack([ct * o[:, 0] - st * o[:, 1] + tf[:, 0], st * o[:, 0] + ct * o[:, 1] + tf[:, 1],
+                             ct * o[:, 2] - st * o[:, 3], st * o[:, 2] + ct * o[:, 3]], dim=1).to(torch.float32).contiguous()
+        matched = wm.match(ranges=ranges, pose=prior, mask=~fresh, **self.knobs)
+        m = matched.to(torch.float64)
+        th = torch.atan2(m[:, 3], m[:, 2]) - torch.atan2(o[:, 3], o[:, 2])
+        th = torch.atan2(torch.sin(th), torch.cos(th))
+        ct, st = torch.cos(th), torch.sin(th)
+        new = torch.stack([m[:, 0] - (ct * o[:, 0] - st * o[:, 1]), m[:, 1] - (st * o[:, 0] + ct * o[:, 1]), th], dim=1)
+        self._tf.copy_(torch.where(fresh.reshape(n, 1), torch.zeros_like(new), new))
+        self._seen.fill_(True)
+        if update:
+            wm.update(ranges=ranges, pose=matched, first=fresh)
+        return matched
 
 
 class LidarFlow:

@@ -44,6 +44,8 @@
  *                          robot's own motion and updated from every scan [unpinned]
  *   ffmp_world_map / ffmp_world_frame -> the /map a ROS graph keeps beside /scan and /odom: int8
  *                          log-odds per WORLD cell, never re-sampled, and its ego view [unpinned]
+ *   ffmp_scan_match     -> the pose corrected against that /map before the scan is integrated: a
+ *                          correlative search over cell shifts and rotation steps [unpinned]
  *   ffmp_scan_flow      -> the flow half of that image (the RGB of "occupancy(MONO) + flow(RGB)",
  *                          src/gym_ffmp/envs/ffmp.py:16) from two scan frames and the two poses: a
  *                          per-cell velocity by block matching with ego-motion compensation [unpinned]
@@ -809,6 +811,60 @@ int ffmp_world_frame(const ffmp_cfg_t* cfg, int64_t n, const float* pose, int64_
                      int32_t unknown, int32_t outside, int32_t occ_thr, int32_t free_thr, void* stream);
 int ffmp_world_frame_check(const ffmp_cfg_t* cfg, int32_t cells, int32_t format, int32_t unknown, int32_t outside,
                            int32_t occ_thr, int32_t free_thr);
+
+/* Scan-to-map matching (an addition within ABI 9: no existing symbol, struct or value changes) — the
+ * localisation half of occupancy-grid mapping: the scan's endpoints are scored against ffmp_world_map's plane
+ * at every whole-cell shift (a, b), |a|, |b| <= R, and every rotation step k, |k| <= T, round the prior pose
+ * (from odometry), and the best candidate's pose is what the scan is then integrated at.  An exhaustive
+ * correlative search with integer scores.  No reference counterpart [unpinned]; the SPEC below is the
+ * definition.  One launch, read-only on the map.
+ * ranges, ranges_stride, n_beams = L (1..FFMP_MAX_BEAMS), range_max (> 0 or +inf): ffmp_scan_frames' conventions.
+ * beams: DEVICE (L, 2) float32, the rounding of {cos, sin}(-pi + l*2pi/L) computed in float64 (the caller's
+ * table).  pose, pose_stride, mask, map, map_env_stride, cells = Wc: exactly ffmp_world_map's, the map const.
+ * turns: DEVICE (2T + 1, 2) float32 {cos, sin} of (k - T) * dtheta, computed on the host in float64 and
+ * rounded; entry T is (1, 0).  n_turns = T in 0..32, radius = R in 0..16 (cells), min_valid >= 0, min_gain >= 0.
+ * Arithmetic: float32, no FMA contraction, operation order as written; a NaN compares false.
+ * Per beam l:
+ *   r = ranges[l];  valid_l = (r > 0) && (r <= range_max) && (r <= FLT_MAX)
+ *   bx = r*beams[l].x;  by = r*beams[l].y
+ * Per rotation k in -T..T, with (rc, rs) = turns[k + T]:
+ *   ck = c*rc - s*rs;  sk = s*rc + c*rs
+ *   wx = (ck*bx - sk*by) + px;  wy = (sk*bx + ck*by) + py
+ *   fp = rintf((wx + wh_f) / res_f);  fq = rintf((wy + wh_f) / res_f)     (ffmp_world_frame's cell rule)
+ *   on_l,k = valid_l && fp >= -R && fp <= Wc-1+R && fq >= -R && fq <= Wc-1+R
+ * float compares; fp and fq are converted to int only where on_l,k holds.  An env with a non-finite pose word
+ * has no beam on.  Score, int32:
+ *   S(k, a, b) = sum over l with on_l,k and (fp+a, fq+b) inside 0..Wc-1 of M[fp+a][fq+b],   a, b in -R..R
+ * — an occupied cell rewards an endpoint, a free cell penalises it, unknown cells and cells off the plane count 0.
+ * Winner: the largest S; ties go to the smaller a*a + b*b, then the smaller |k|, then the smaller k, then the
+ * smaller a, then the smaller b — a total order, so the order of the reduction does not show.
+ * Gate: valid = the number of beams with valid_l.  status = 0 if a pose word is non-finite, or valid < min_valid,
+ * or S_best - S(0,0,0) < min_gain, or the winner is (0, 0, 0); otherwise status = 1.
+ * Outputs, DEVICE memory, each written only when non-NULL (not all three NULL):
+ *   pose_out (n, 4) float32, 16-byte aligned: status 0 — the four prior words copied bit for bit; status 1 —
+ *     {px + (float)a*res_f, py + (float)b*res_f, ck, sk} of the winner (the layout ffmp_world_map takes)
+ *   info (n, 8) int32, 16-byte aligned: {status, k, a, b, S_best, S(0,0,0), valid, 0}; k, a, b are 0 when
+ *     status is 0; both scores are 0 for a non-finite pose
+ *   volume (n, 2T+1, 2R+1, 2R+1) int32: every S(k, a, b) at [k + T][a + R][b + R]
+ * mask[e] == 0 leaves all of env e's outputs unwritten.
+ * flags: FFMP_MATCH_GLOBAL — gather the map's bytes from global memory.  That is what the kernel does with or
+ * without it: the other form, a copy in LDS of the box round the robot that holds every endpoint, gave the same
+ * bits, was measured slower and is not kept; the flag is accepted and changes nothing.
+ * FFMP_E_ARG, with a message and before any HIP call, for: what ffmp_world_map refuses of cfg, cells, n_beams,
+ * range_max, ranges_stride, pose_stride, map_env_stride and the map's alignment; radius, n_turns, min_valid or
+ * min_gain out of range; unknown flag bits; ranges, beams, pose, map or turns NULL; all three outputs NULL; a
+ * misaligned output; an output whose bytes overlap the map's; n < 0 or too large for one launch.  n == 0:
+ * nothing is launched.
+ * ffmp_scan_match_check: the checks that need no pointer, no launch (the kernel's LDS is static, 27 KiB, whatever
+ * the shape: its budget is checked when the library is compiled). */
+#define FFMP_MATCH_GLOBAL 1
+int ffmp_scan_match(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t ranges_stride, int32_t n_beams,
+                    const float* beams, const float* pose, int64_t pose_stride, const uint8_t* mask, const int8_t* map,
+                    int64_t map_env_stride, int32_t cells, const float* turns, int32_t n_turns, int32_t radius, float range_max,
+                    int32_t min_valid, int32_t min_gain, float* pose_out, int32_t* info, int32_t* volume, int32_t flags,
+                    void* stream);
+int ffmp_scan_match_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t cells, int32_t radius, int32_t n_turns,
+                          float range_max, int32_t min_valid, int32_t min_gain, int32_t flags);
 
 /* Motion flow estimated from the scan (an addition within ABI 9: no existing symbol, struct or value
  * changes): the sensor-side counterpart of the flow planes of cfg.flow.  Two scan frames `lag` updates
