@@ -1,7 +1,12 @@
 """make_temporal_maps over k frames (src/train.py:474-486 with INPUT_CHANNELS = k mono frames,
 :66-69) served from the frame ring by ffmp_temporal_maps, against the oracle's TemporalStack fed
 with the oracle env's newest frames (is_first = the step's auto-reset, or the initial reset).
-Bit-exact: the frames are 0/255 bytes or floats copied, never computed."""
+Bit-exact: the frames are 0/255 bytes or floats copied, never computed.
+
+CFG's episodes all end by the max_steps truncation, so every env has the same age at every step.  The cases
+named G100 / G36 / G12 / G8 run the configs of tests/series_cases.py instead: episodes that end by collisions and
+goals at different steps in different envs (the per-env clamp of ffmp_temporal_maps), on grids whose planes are
+ragged for the gather kernel (2500 / 625, 81, 9 and 4 sixteen-byte vectors)."""
 import numpy as np
 import pytest
 import torch
@@ -9,6 +14,7 @@ import torch
 from flow_field_based_motion_planner_amd import FFMPConfig
 from flow_field_based_motion_planner_amd.vec_env import FFMPVec
 from oracle.ffmp_oracle import OracleVecEnv, TemporalStack
+from tests import series_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -34,16 +40,33 @@ def _check(env, stacks, tag):
         assert got.shape == want.shape, (tag, k, got.shape, want.shape)
         bad = np.argwhere((got != want).any(axis=(2, 3)))
         assert bad.size == 0, f"{tag} k={k}: (env, channel) mismatches {bad[:8].tolist()}"
+        if k <= 2:  # without `out` that was a view of state_m: through the kernel too
+            G = env.cfg.grid
+            buf = torch.empty(env.num_envs, k, G, G, dtype=env.state_m.dtype, device=env.device)
+            got = env.temporal_maps(k, out=buf).cpu().numpy().astype(np.float32)
+            bad = np.argwhere((got != want).any(axis=(2, 3)))
+            assert bad.size == 0, f"{tag} k={k} gathered: (env, channel) mismatches {bad[:8].tolist()}"
 
 
-@pytest.mark.parametrize("window,seamless,fmt", [(4, True, "f32"), (6, True, "u8f16"), (5, False, "f32"),
-                                                 (2, False, "f32")])
-def test_temporal_maps_match_reference_stack(window, seamless, fmt):
+ROWS = [(4, True, "f32"), (6, True, "u8f16"), (5, False, "f32"), (2, False, "f32")]
+# the present cases keep their ids; G100 and G12 take every (window, ring, format) row, G36 and G8 one float32 and
+# one u8f16 row each
+STACK_CASES = ([pytest.param(None, *row, id="-".join(map(str, row))) for row in ROWS]
+               + [pytest.param(name, *row, id="-".join(map(str, (name,) + row)))
+                  for name in ("G100", "G12") for row in ROWS]
+               + [pytest.param(name, *row, id="-".join(map(str, (name,) + row)))
+                  for name in ("G36", "G8") for row in ROWS[:2]])
+
+
+@pytest.mark.parametrize("case,window,seamless,fmt", STACK_CASES)
+def test_temporal_maps_match_reference_stack(case, window, seamless, fmt):
     n, steps = 24, 22
-    env = FFMPVec(n, CFG, device="cuda:0", frame_window=window, seamless=seamless if window > 2 else None,
+    cfg = CFG if case is None else series_cases.config(case)
+    mix = series_cases.AgeMix()
+    env = FFMPVec(n, cfg, device="cuda:0", frame_window=window, seamless=seamless if window > 2 else None,
                   obs_format=fmt, autotune=False)
     assert env.ring == ("contiguous" if window == 2 else "seamless" if seamless else "wrap")
-    ref = OracleVecEnv(CFG, n)
+    ref = OracleVecEnv(cfg, n)
     env.reset()
     ref.reset()
     # a wrapping ring keeps W - 1 frames once it has wrapped: k = W is refused up front,
@@ -65,17 +88,22 @@ def test_temporal_maps_match_reference_stack(window, seamless, fmt):
         assert np.array_equal(env.state_m.cpu().numpy().astype(np.float32), ref.state_m), f"state_m step {s}"
         _push(stacks, ref, ref.done)
         resets += int(ref.done.sum())
+        mix.note(ref)
         _check(env, stacks, f"step {s}")
     assert resets > n, resets  # episodes end at every lag position
+    if case is not None:  # and at different steps in different envs (tests/test_series_cases_host.py)
+        mix.check(n, ref.state_m[:, 1])
 
 
-def test_temporal_maps_masked_reset_and_reload():
-    n, W = 16, 5
-    env = FFMPVec(n, CFG.replace(max_steps=0), device="cuda:0", frame_window=W, autotune=False)
-    ref = OracleVecEnv(CFG.replace(max_steps=0), n)
+def _masked_reset_and_reload(cfg, n, W, seamless, fmt, mix=None, deep=None):
+    cfg = cfg.replace(max_steps=0)
+    kw = dict(device="cuda:0", frame_window=W, seamless=seamless, obs_format=fmt, autotune=False)
+    env = FFMPVec(n, cfg, **kw)
+    ref = OracleVecEnv(cfg, n)
     env.reset()
     ref.reset()
-    stacks = _stacks(ref, [3, 5])
+    deep = env.max_temporal_frames if deep is None else deep  # W, or W - 1 for the wrapping ring
+    stacks = _stacks(ref, [3, deep])
     _push(stacks, ref, np.ones(n, bool))
     rng = np.random.default_rng(5)
     for s in range(7):
@@ -83,6 +111,10 @@ def test_temporal_maps_masked_reset_and_reload():
         env.step(torch.as_tensor(a, device="cuda:0"))
         ref.step(a)
         _push(stacks, ref, ref.done)
+        if mix is not None:
+            mix.note(ref)
+    if mix is not None:
+        mix.check(n, ref.state_m[:, 1])
     mask = np.zeros(n, bool)
     mask[::3] = True
     env.reset(mask=torch.as_tensor(mask, device="cuda:0"))
@@ -93,7 +125,7 @@ def test_temporal_maps_masked_reset_and_reload():
     _check(env, stacks, "masked reset")
     # a reload re-rasters the [older, newest] pair only: deeper lags are refused until stepped again
     sd = env.state_dict()
-    env2 = FFMPVec(n, CFG.replace(max_steps=0), device="cuda:0", frame_window=W, autotune=False)
+    env2 = FFMPVec(n, cfg, **kw)
     env2.load_state_dict(sd)
     assert torch.equal(env2.temporal_maps(2), env.temporal_maps(2))
     with pytest.raises(RuntimeError):
@@ -104,6 +136,22 @@ def test_temporal_maps_masked_reset_and_reload():
         ref.step(a)
         _push(stacks, ref, ref.done)
     _check(env2, stacks, "after reload")
+
+
+def test_temporal_maps_masked_reset_and_reload():
+    _masked_reset_and_reload(CFG, 16, 5, None, "f32", deep=5)
+
+
+MASKED_ROWS = [(5, None, "f32"), (5, False, "f32"), (4, True, "u8f16")]
+
+
+@pytest.mark.parametrize("case,window,seamless,fmt",
+                         [(name,) + row for name in ("G100", "G12") for row in MASKED_ROWS]
+                         + [(name,) + row for name in ("G36", "G8") for row in (MASKED_ROWS[0], MASKED_ROWS[2])])
+def test_temporal_maps_masked_reset_and_reload_mixed_ages(case, window, seamless, fmt):
+    """The same on the configs of tests/series_cases.py, both formats and both rings: the envs differ in age
+    before the masked reset, not only after it."""
+    _masked_reset_and_reload(series_cases.config(case), 16, window, seamless, fmt, mix=series_cases.AgeMix())
 
 
 def test_temporal_maps_out_and_errors():
