@@ -6,7 +6,8 @@ LIB = flow_field_based_motion_planner_amd/lib/libffmp.so
 CSRC = flow_field_based_motion_planner_amd/csrc
 SRC = $(CSRC)/ffmp_kernels.hip $(CSRC)/ffmp_ring.hip $(CSRC)/ffmp_conv.hip $(CSRC)/ffmp_nav.hip \
       $(CSRC)/ffmp_visible.hip $(CSRC)/ffmp_scan.hip $(CSRC)/ffmp_flowest.hip $(CSRC)/ffmp_predict.hip \
-      $(CSRC)/ffmp_potential.hip $(CSRC)/ffmp_dwa.hip $(CSRC)/ffmp_worldmap.hip $(CSRC)/ffmp_match.hip
+      $(CSRC)/ffmp_potential.hip $(CSRC)/ffmp_dwa.hip $(CSRC)/ffmp_worldmap.hip $(CSRC)/ffmp_match.hip \
+      $(CSRC)/ffmp_reloc.hip
 HDRS = $(CSRC)/ffmp_device.h $(CSRC)/ffmp_host.h $(CSRC)/ffmp_raster_plan.h include/ffmp.h
 OBJDIR = build/obj
 OBJ = $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRC))

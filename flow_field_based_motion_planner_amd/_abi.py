@@ -169,6 +169,11 @@ _SIGS = {
     "ffmp_scan_match": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _I32, _I32,
                                   C.c_float, _I32, _I32, _P, _P, _P, _I32, _P]),
     "ffmp_scan_match_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, C.c_float, _I32, _I32, _I32]),
+    # wide-prior and global relocalisation (an addition within ABI 9): the same winner by a pruned two-level search
+    "ffmp_scan_relocalize": (C.c_int, [C.POINTER(CfgT), _I64, _P, _I64, _I32, _P, _P, _I64, _P, _P, _I64, _I32, _P, _I32, _I32,
+                                       _I32, C.c_float, _I32, _I32, _I32, _P, _P, _P, _P, _I64, _I32, _P]),
+    "ffmp_scan_relocalize_check": (C.c_int, [C.POINTER(CfgT), _I32, _I32, _I32, _I32, _I32, C.c_float, _I32, _I32, _I32]),
+    "ffmp_scan_relocalize_work": (_I64, [_I32, _I32, _I32, _I32]),
     # motion flow estimated from two scan frames (an addition within ABI 9): block matching, ego-motion compensated
     "ffmp_scan_flow": (C.c_int, [C.POINTER(CfgT), _I64, _P, _P, _I64, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _I64, _I32,
                                  C.c_float, _I32, _I32, _I32, _I32, _P]),
@@ -299,6 +304,7 @@ RASTER_DIRECT = 2048  # beside RASTER_WAVES, two-launch raster: blocks without L
 VISIBLE_NOCULL = 1  # FFMP_VISIBLE_NOCULL: ffmp_visible_frames without its culls (the same bits)
 SCAN_PLAIN = 1  # FFMP_SCAN_PLAIN: ffmp_scan_frames with the SPEC's bisection for every cell (the same bits)
 MATCH_GLOBAL = 1  # FFMP_MATCH_GLOBAL: ffmp_scan_match gathering from global memory — what it always does; accepted, no effect
+RELOC_EXHAUSTIVE = 1  # FFMP_RELOC_EXHAUSTIVE: ffmp_scan_relocalize refining every block (the same pose and info[0:7])
 
 
 def set_tuning(key: int, value: int) -> int:

@@ -3022,6 +3022,89 @@ class WorldMap:
             return out
         return (out,) + ((info,) if detail else ()) + ((vol,) if volume else ())
 
+    _reloc_work = None  # the relocalisation's workspace, kept by its size
+
+    def relocalize(self, ranges: Optional[torch.Tensor] = None, pose: Optional[torch.Tensor] = None, radius: Optional[int] = None,
+                   turns: int = 90, dtheta: Optional[float] = None, block: int = 8, min_valid: Optional[int] = None,
+                   min_score: Optional[int] = None, min_gain: int = 0, range_max: Optional[float] = None, refine: bool = True,
+                   detail: bool = False, bounds: bool = False, out: Optional[torch.Tensor] = None,
+                   mask: Optional[torch.Tensor] = None, flags: int = 0):
+        """The pose found again on the map over a wide window or with no prior at all (include/ffmp.h
+        ffmp_scan_relocalize): match()'s winner over `radius` up to 1024 cells and `turns` up to 512 steps of
+        `dtheta`, by a pruned two-level search with blocks of `block` x `block` shifts — the same bits as the
+        exhaustive search.  Six launches on the current stream, read-only on the map; (N, 4) float32.
+        pose=None: no prior — the plane's centre with yaw 0, radius cells // 2 and dtheta 2 pi / (2 turns + 1),
+        the whole plane and the full circle.  With a pose: radius 32 and match()'s dtheta by default.
+        ranges, min_valid, min_gain, range_max, out, mask: match()'s.  min_score: the least score that is believed
+        (None: no such rule).  refine: follow the search with one match() launch at its answer on the envs of
+        status 1 — radius 2, match()'s default dtheta, turns = min(32, ceil(dtheta / fine / 2)) — which recovers
+        the angular resolution the coarse rotation step gave up.  detail: also return the search's info (N, 8)
+        int32 {status, k, a, b, S_best, S(0,0,0), valid, refined blocks}; bounds: also return every U
+        (N, 2 turns + 1, nb, nb) int32.  flags: _abi.RELOC_EXHAUSTIVE refines every block (the same pose)."""
+        env = self.env
+        env._check_open()
+        self._check()
+        n = env.num_envs
+        if ranges is None:
+            if env.lidar is None:
+                raise ValueError("WorldMap.relocalize: the env has n_beams == 0, pass ranges=")
+            if env._needs_reset:
+                raise RuntimeError("call reset() before WorldMap.relocalize()")
+            ranges = env.lidar
+        elif not isinstance(ranges, torch.Tensor) or ranges.dim() != 2 or ranges.shape[0] != n or ranges.dtype != torch.float32 \
+                or not ranges.is_contiguous() or ranges.device != env.device:
+            raise ValueError(f"ranges must be a contiguous float32 tensor of shape ({n}, L) on {env.device}")
+        L, T, B = int(ranges.shape[1]), int(turns), int(block)
+        fine = env.cfg.res / env.cfg.lidar_range
+        if pose is None:
+            pose = self._match_table("centre", lambda: np.tile(np.array([[0.0, 0.0, 1.0, 0.0]], np.float32), (n, 1)))
+            R = self.cells // 2 if radius is None else int(radius)
+            dtheta = 2.0 * math.pi / (2 * T + 1) if dtheta is None else float(dtheta)
+        else:
+            pose = self._pose(pose)
+            R = 32 if radius is None else int(radius)
+            dtheta = fine if dtheta is None else float(dtheta)
+        min_valid = max(8, L // 6) if min_valid is None else int(min_valid)
+        min_score = -2 ** 31 if min_score is None else int(min_score)
+        rm = self.knobs[1] if range_max is None else float(range_max)
+        _abi.check(env.lib.ffmp_scan_relocalize_check(C.byref(env._cfg_c), L, self.cells, R, T, B, rm, min_valid, int(min_gain),
+                                                      int(flags)), "ffmp_scan_relocalize_check")
+        mask = self._mask(mask)
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float32, device=env.device)
+            if mask is not None:
+                out.copy_(pose[:, 0:4])
+        elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, 4) or out.dtype != torch.float32 \
+                or not out.is_contiguous() or out.device != env.device:
+            raise ValueError(f"out must be a contiguous float32 tensor of shape ({n}, 4) on {env.device}")
+        info = torch.zeros((n, 8), dtype=torch.int32, device=env.device) if (detail or refine) else None
+        nb = (2 * R + B) // B
+        U = torch.zeros((n, 2 * T + 1, nb, nb), dtype=torch.int32, device=env.device) if bounds else None
+        per_env = int(env.lib.ffmp_scan_relocalize_work(self.cells, R, T, B))
+        if per_env < 0:
+            _abi.check(per_env, "ffmp_scan_relocalize_work")
+        if self._reloc_work is None or self._reloc_work.numel() != n * per_env:
+            self._reloc_work = None
+            self._reloc_work = torch.empty((n * per_env,), dtype=torch.uint8, device=env.device)
+        work = self._reloc_work
+        beams = self._match_table(L, lambda: beam_dirs(L))
+        table = self._match_table((T, dtheta), lambda: turn_table(T, dtheta))
+        with torch.cuda.device(env.device):
+            _abi.check(env.lib.ffmp_scan_relocalize(C.byref(env._cfg_c), n, ranges.data_ptr(), ranges.stride(0), L, beams.data_ptr(),
+                                                    pose.data_ptr(), pose.stride(0), _ptr(mask), self._plane.data_ptr(),
+                                                    self.cells * self.cells, self.cells, table.data_ptr(), T, R, B, rm, min_valid,
+                                                    int(min_gain), min_score, out.data_ptr(), _ptr(info), _ptr(U), work.data_ptr(),
+                                                    work.numel(), int(flags), env._stream()), "ffmp_scan_relocalize")
+        if refine:
+            found = info[:, 0] == 1
+            if mask is not None:
+                found = found & mask.bool()
+            self.match(ranges=ranges, pose=out.clone(), radius=2, turns=min(32, max(0, math.ceil(dtheta / fine / 2.0))),
+                       min_valid=min_valid, range_max=rm, out=out, mask=found)
+        if not detail and not bounds:
+            return out
+        return (out,) + ((info,) if detail else ()) + ((U,) if bounds else ())
+
     def localizer(self, radius: int = 2, turns: int = 2, dtheta: Optional[float] = None, min_valid: Optional[int] = None,
                   min_gain: int = 0, range_max: Optional[float] = None) -> "Localizer":
         """A holder that keeps the per-env map <- odom transform and corrects every odometry pose against this
@@ -3080,6 +3163,34 @@ class Localizer:
         if update:
             wm.update(ranges=ranges, pose=matched, first=fresh)
         return matched
+
+    def relocalize(self, odom: torch.Tensor, ranges: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                   **knobs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Recovery for the envs of `mask` ((N,) bool or uint8; None = all) whose transform is lost: the pose is
+        searched on the whole map with no prior (WorldMap.relocalize(pose=None, **knobs)) and the `transform` rows
+        of the envs that came back with status 1 are recomputed from it and `odom`, with step()'s float64
+        formulas; every other row stays as it was, and the map is not updated.  Returns (pose (N, 4) float32 —
+        the rows not searched or not found hold the plane's centre —, status (N,) int32)."""
+        wm = self.map
+        env = wm.env
+        if odom is None:
+            raise ValueError("Localizer.relocalize: odom is required")
+        odom = wm._pose(odom)
+        n = env.num_envs
+        knobs = dict(knobs, detail=True, bounds=False)
+        pose, info = wm.relocalize(ranges=ranges, pose=None, mask=mask, **knobs)[0:2]
+        found = info[:, 0] == 1
+        if mask is not None:
+            found = found & wm._mask(mask).bool()
+        o = odom.to(torch.float64)
+        m = pose.to(torch.float64)
+        th = torch.atan2(m[:, 3], m[:, 2]) - torch.atan2(o[:, 3], o[:, 2])
+        th = torch.atan2(torch.sin(th), torch.cos(th))
+        ct, st = torch.cos(th), torch.sin(th)
+        new = torch.stack([m[:, 0] - (ct * o[:, 0] - st * o[:, 1]), m[:, 1] - (st * o[:, 0] + ct * o[:, 1]), th], dim=1)
+        self._tf.copy_(torch.where(found.reshape(n, 1), new, self._tf))
+        self._seen.copy_(self._seen | found)
+        return pose, torch.where(found, torch.ones_like(info[:, 0]), torch.zeros_like(info[:, 0]))
 
 
 class LidarFlow:

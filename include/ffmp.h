@@ -46,6 +46,8 @@
  *                          log-odds per WORLD cell, never re-sampled, and its ego view [unpinned]
  *   ffmp_scan_match     -> the pose corrected against that /map before the scan is integrated: a
  *                          correlative search over cell shifts and rotation steps [unpinned]
+ *   ffmp_scan_relocalize -> the same winner over the whole plane and the full circle, with no prior:
+ *                          a pruned two-level correlative search [unpinned]
  *   ffmp_scan_flow      -> the flow half of that image (the RGB of "occupancy(MONO) + flow(RGB)",
  *                          src/gym_ffmp/envs/ffmp.py:16) from two scan frames and the two poses: a
  *                          per-cell velocity by block matching with ego-motion compensation [unpinned]
@@ -865,6 +867,72 @@ int ffmp_scan_match(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64
                     void* stream);
 int ffmp_scan_match_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t cells, int32_t radius, int32_t n_turns,
                           float range_max, int32_t min_valid, int32_t min_gain, int32_t flags);
+
+/* Wide-prior and global relocalisation (an addition within ABI 9: no existing symbol, struct, value or limit
+ * changes): ffmp_scan_match's winner over a window far larger than its own — radius = R in 0..1024 cells,
+ * n_turns = T in 0..512 — found by a pruned two-level correlative search (Olson 2009; the branch and bound of
+ * 2-D SLAM stacks) in place of the exhaustive one.  The scores are integer sums of int8 cells, so the bound
+ * below is exact and the pruned search returns the same winner, bit for bit, as the exhaustive search under
+ * ffmp_scan_match's tie order.  No reference counterpart [unpinned]; the SPEC below is the definition.  Six
+ * launches on the caller's stream, capturable, read-only on the map.
+ * ranges, ranges_stride, n_beams, beams, pose, pose_stride, mask, map, map_env_stride, cells = Wc, turns (the
+ * caller's (2T + 1, 2) table), range_max, min_valid, min_gain, pose_out, info, stream: exactly ffmp_scan_match's.
+ * block = B in {2, 4, 8, 16}; min_score: any int32; work, work_bytes: a DEVICE workspace of the caller's,
+ * 16-byte aligned, at least n * ffmp_scan_relocalize_work(cells, radius, n_turns, block) bytes.
+ * The fine score S(k, a, b), a, b in -R..R, k in -T..T, is ffmp_scan_match's, word for word: valid_l, bx/by,
+ * ck/sk, fp/fq with rintf, on_l,k with this call's R, the int32 sum over the cells inside the plane, fp and fq
+ * converted to int only where on_l,k holds.
+ * New definitions:
+ *   M'[p][q] = M[p][q] inside 0..Wc-1, else 0
+ *   X[p][q] = max over 0 <= i, j < B of M'[p+i][q+j], for any integer p, q (0 where the window misses the plane)
+ *   nb = (2R + B) / B (integer division);  a0(j) = -R + j*B
+ *   block (k, A, Cc), A, Cc in 0..nb-1, holds the shifts a in a0(A)..min(a0(A)+B-1, R), and b likewise from Cc
+ *   U(k, A, Cc) = sum over l with on_l,k of X[fp_l + a0(A)][fq_l + a0(Cc)], int32
+ * U >= S for every shift of the block: each term of S is one of the cells X takes the maximum over, or 0 <= X
+ * where the cell is off the plane.
+ * Schedule (part of the SPEC: it defines info[7]):
+ *   1. the seed is the block with the largest U; ties go to the smallest linear index ((k+T)*nb + A)*nb + Cc
+ *   2. S1 = the largest S over the seed's shifts
+ *   3. the refined set = every block with U >= S1
+ *   4. the winner = the best shift over the refined set under ffmp_scan_match's total order: larger S, then
+ *      smaller a*a + b*b, then smaller |k|, smaller k, smaller a, smaller b
+ * This is the exhaustive winner:
+ *   the exhaustive winner has S >= S1,
+ *   its block has U >= S, so it is in the refined set,
+ *   and the same holds for every candidate that ties with it.
+ * Gate: ffmp_scan_match's — status 0 for a non-finite pose word, valid < min_valid, S_best - S(0,0,0) < min_gain,
+ * or the winner (0, 0, 0) — plus one rule: status 0 if S_best < min_score.  INT32_MIN disables the rule.
+ * Outputs, DEVICE memory, each written only when non-NULL (not all three NULL):
+ *   pose_out (n, 4) float32 and info (n, 8) int32, 16-byte aligned: exactly ffmp_scan_match's, but info[7] = the
+ *     size of the refined set
+ *   bounds (n, 2T+1, nb, nb) int32, 4-byte aligned: every U(k, A, Cc) at [k + T][A][Cc]
+ * There is no volume: most of it is never computed.  An env with a non-finite pose word has no beam on: both
+ * scores are 0 and the status is 0.  mask[e] == 0 leaves all of env e's outputs unwritten.
+ * flags: FFMP_RELOC_EXHAUSTIVE — the refined set is every block: the same pose_out and info[0..6], info[7] =
+ * (2T+1)*nb*nb.
+ * ffmp_scan_relocalize_work: the workspace bytes per env, a multiple of 16; a host function with no HIP call;
+ * negative (FFMP_E_ARG, with a message) for cells, radius, n_turns or block out of range; it does not shrink
+ * when radius or n_turns grows.  Per env the bytes hold, in this order: a 64-byte header {refined count, S1,
+ * S(0,0,0), valid, the seed's index, the beams on over all rotations}; per rotation the largest (U, smallest index), 2T+1 uint64; the partial
+ * winners of the refinement's workgroups; per rotation the number of beams on, 2T+1 int32; per rotation the on
+ * beams' cell pairs (fp + R) << 16 | (fq + R), room for FFMP_MAX_BEAMS each; U, (2T+1)*nb*nb int32; the
+ * refined blocks' indices, as many int32; X, one byte per cell of the plane extended by B - 1 to either side,
+ * stored X[p mod B][q mod B][p div B][q div B].  Nothing in it outlives the call.
+ * FFMP_E_ARG, with a message and before any HIP call, for: everything ffmp_scan_match refuses of the shared
+ * arguments; radius, n_turns or block outside the limits above; all three outputs NULL; work NULL or work_bytes <
+ * n * bytes per env; a misaligned bounds (4 bytes) or work (16 bytes); an output or the workspace whose bytes
+ * overlap the map's; an output that overlaps the workspace.  n == 0: nothing is launched.
+ * ffmp_scan_relocalize_check: the checks that need no pointer, no launch. */
+#define FFMP_RELOC_EXHAUSTIVE 1
+int ffmp_scan_relocalize(const ffmp_cfg_t* cfg, int64_t n, const float* ranges, int64_t ranges_stride, int32_t n_beams,
+                         const float* beams, const float* pose, int64_t pose_stride, const uint8_t* mask, const int8_t* map,
+                         int64_t map_env_stride, int32_t cells, const float* turns, int32_t n_turns, int32_t radius,
+                         int32_t block, float range_max, int32_t min_valid, int32_t min_gain, int32_t min_score,
+                         float* pose_out, int32_t* info, int32_t* bounds, void* work, int64_t work_bytes, int32_t flags,
+                         void* stream);
+int ffmp_scan_relocalize_check(const ffmp_cfg_t* cfg, int32_t n_beams, int32_t cells, int32_t radius, int32_t n_turns,
+                               int32_t block, float range_max, int32_t min_valid, int32_t min_gain, int32_t flags);
+int64_t ffmp_scan_relocalize_work(int32_t cells, int32_t radius, int32_t n_turns, int32_t block);
 
 /* Motion flow estimated from the scan (an addition within ABI 9: no existing symbol, struct or value
  * changes): the sensor-side counterpart of the flow planes of cfg.flow.  Two scan frames `lag` updates
